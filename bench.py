@@ -7,13 +7,20 @@ Workload (BASELINE.json configs[1]): ResNet-50 W8A8 fake-quant forward, syntheti
 Activations come from one real fp32 forward of a random-init ResNet-50 (seed 0) on U(0,1) images
 (seed 1234 + rank) and stay resident in HBM; a "step" quantize-dequantizes all of them once.
 Encodings are computed first (TF-Enhanced activations, TF-Enhanced per-channel weights =
-QuantizationSimModel's default scheme) and that compute_encodings wall-clock is reported too.
+QuantizationSimModel's default scheme).
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what the headline needs and no more: the
+forward, one compute_encodings call, W untimed and K timed steps, the result line. `--dump-outputs
+DIR` also writes what the last timed step computed (below). Everything else the benchmark measures
+or checks is behind `--full`: the compute_encodings wall-clock (its repeated calls and calibration
+plans), the drop-in surface, the CPU baseline with its parity check, the collectives' timings at
+N > 1, `--force-exchange`, and the secondary configs.
 
 Multi-GPU: one process per GPU (torch.distributed, RCCL). Each rank runs its own batch (weak
 scaling, no data-path collective); calibration is sharded per sample across ranks with one RCCL
 exchange of the packed statistics per batch (aimet_amd.distributed).
 
-At N=1 the line also carries BASELINE configs 3 and 5 (`secondary`), each run by its own benchmark
+With --full at N=1 the line also carries BASELINE configs 3 and 5 (`secondary`), each run by its own benchmark
 in a child process after the headline (benchmarks/adaround_mobilenet.py: MobileNet-v2 AdaRound, all
 53 layers x 10k iterations; benchmarks/llama_qat.py: Llama-3-8B W4A16 QAT at seq 2048, mb 1, full
 model, beside the same step without quantizers), within a time budget that keeps the whole run
@@ -47,6 +54,8 @@ BYTES_QDQ = 8            # fp32 read + fp32 write per element
 # report null). The same figure as rounds 1-4 (the QDQ kernels are unchanged).
 TRAFFIC_GB = 23.0734
 TRAFFIC_ELEMS = 2883971072
+# --dump-outputs: elements kept of each output tensor (109 tensors x 512 KiB = 54.5 MiB at the most)
+DUMP_ELEMS = 1 << 17
 
 
 def parse():
@@ -55,6 +64,12 @@ def parse():
     p.add_argument("--steps", type=int, default=100)   # ~0.37 s timed region at N=1
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--batch", type=int, default=256)
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything beside the headline: compute_encodings wall-clock, "
+                        "drop-in surface, CPU baseline + parity, collectives at N > 1, secondary configs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the QDQ outputs of the last step as DIR/<name>.npy (float32; "
+                        "tensors above %d elements as a fixed, seeded sample of that many)" % DUMP_ELEMS)
     p.add_argument("--cpu-sample-images", type=int, default=32,
                    help="images of each activation tensor (plus all weights) timed on the CPU oracle")
     p.add_argument("--no-cpu-baseline", action="store_true")
@@ -73,8 +88,12 @@ def parse():
                    help="seconds from the start of bench.py by which the secondary configs must end")
     p.add_argument("--force-exchange", action="store_true",
                    help="at N=1 form a world-size-1 RCCL group before any GPU call and time the sharded "
-                        "calibration's staged form (both packed collectives through RCCL) beside the headline")
-    return p.parse_args()
+                        "calibration's staged form (both packed collectives through RCCL) beside the headline "
+                        "(needs --full)")
+    args = p.parse_args()
+    if args.force_exchange and not args.full:
+        p.error("--force-exchange times a configuration beside the headline: give --full with it")
+    return args
 
 
 def _free_port():
@@ -408,6 +427,63 @@ def cpu_baseline(acts, weights, act_enc, w_enc, images, act_outs, w_outs):
     return res
 
 
+def compute_encodings_wall_clock(args, world, acts, weights):
+    """--full: the compute_encodings wall-clock: the first call of the process (cold: code objects
+    load, pools grow, quantizers created), the median of --enc-reps calls on fresh quantizers, the
+    median of --enc-reps calls that reset and recompute the same quantizers
+    (QuantizationSimModel.compute_encodings on an existing sim), and the calibration plan's runs
+    (the reported compute_encodings_s). Returns the encodings of the plan's last run, the sim's
+    quantizers, the plan (closed by the caller) and the figures."""
+    act_enc, w_enc, enc_cold, aq, wq = compute_encodings(acts, weights)
+    fresh, warm = [], []
+    for _ in range(args.enc_reps):
+        del aq, wq
+        act_enc, w_enc, secs, aq, wq = compute_encodings(acts, weights)
+        fresh.append(secs)
+    for _ in range(args.enc_reps):
+        act_enc, w_enc, secs, aq, wq = compute_encodings(acts, weights, (aq, wq))
+        warm.append(secs)
+    enc_resident = sorted(warm)[len(warm) // 2] if warm else enc_cold
+    enc_fresh = sorted(fresh)[len(fresh) // 2] if fresh else enc_cold
+    # the headline: a calibration plan over the sim's quantizers and the resident activations,
+    # prepared once (as the quantizers are created once with the sim), each timed run a reset +
+    # recompute of every quantizer (aimet_amd.calibration.CalibrationPlan). Sharded at N > 1.
+    from aimet_amd.calibration import CalibrationPlan
+    cplan = CalibrationPlan(aq, [t for _, t in acts], wq, [w for _, w in weights])
+    enc_spans, enc_phases = [], []
+    enc_seconds, (a_res, w_res), enc_runs_ms = time_plan(cplan, max(1, args.plan_reps), spans=enc_spans,
+                                                         phases=enc_phases)
+    # the same on quantizers made for the plan alone (a new sim), for comparison
+    nq, nw = make_quantizers(acts, weights)
+    nplan = CalibrationPlan(nq, [t for _, t in acts], nw, [w for _, w in weights])
+    new_spans = []
+    enc_new_s, _, _ = time_plan(nplan, max(1, args.plan_reps), spans=new_spans)
+    nplan.close()
+    del nq, nw
+    plan_act, plan_w = [e for e, _ in a_res], [e for e, _ in w_res]
+    enc_plan_equal = ([e.to_tuple() for e in plan_act] == [e.to_tuple() for e in act_enc] and
+                      [[x.to_tuple() for x in es] for es in plan_w] == [[x.to_tuple() for x in es] for es in w_enc])
+    act_enc, w_enc = plan_act, plan_w
+    enc_exchange = None
+    if args.force_exchange and world == 1:
+        # the sharded calibration's staged form on this rank (stage 1, RCCL MAX, stage 2, RCCL SUM,
+        # stage 4) over a world-size-1 group: the per-rank cost the 1 -> N curve starts from.
+        # Quantizers of their own (the plan binds them to the packed exchange buffers).
+        xq, xw = make_quantizers(acts, weights)
+        xplan = CalibrationPlan(xq, [t for _, t in acts], xw, [w for _, w in weights], force_exchange=True)
+        x_s, (xa, xwr), x_runs = time_plan(xplan, max(1, args.plan_reps))
+        enc_exchange = {"seconds": round(x_s, 4), "dist_backend": dist.get_backend(),
+                        "world_formed": dist.get_world_size(),
+                        "equal_to_headline": [e.to_tuple() for e, _ in xa] == [e.to_tuple() for e in act_enc] and
+                        [[x.to_tuple() for x in es] for es, _ in xwr] == [[x.to_tuple() for x in es] for es in w_enc]}
+        xplan.close()
+        del xq, xw
+    return act_enc, w_enc, aq, wq, cplan, {
+        "seconds": enc_seconds, "cold": enc_cold, "fresh": enc_fresh, "resident": enc_resident,
+        "runs_ms": enc_runs_ms, "spans": enc_spans, "phases": enc_phases, "new_s": enc_new_s,
+        "new_spans": new_spans, "plan_equal": enc_plan_equal, "exchange": enc_exchange}
+
+
 def time_exchange(dev, act_quantizers, reps=20):
     """The two collectives of one sharded calibration batch (aimet_amd.distributed) at the packed
     sizes this workload exchanges: {-min, max} of every activation quantizer (all_reduce MAX) and
@@ -437,6 +513,20 @@ def _max_over_ranks(v, dev):
     t = torch.tensor([v], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+def dump_outputs(path, named):
+    """--dump-outputs: every (name, tensor) of `named` as path/<name>.npy in float32. A tensor above
+    DUMP_ELEMS elements is written as that many of its elements (row-major positions drawn once
+    from a generator seeded by the tensor's place in the list, sorted): the same positions in
+    every run and every build, so two dumps compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    for k, (name, t) in enumerate(named):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_ELEMS:
+            idx = np.sort(np.random.default_rng(k).integers(0, flat.numel(), DUMP_ELEMS, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), flat.cpu().numpy().astype(np.float32, copy=False))
 
 
 def _run_child(cmd, timeout, env=None):
@@ -510,7 +600,8 @@ def main():
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
-    if (world_env is None and args.gpus == 1 and not args.no_secondary and not os.environ.get("AIMET_BENCH_CHILD")
+    if (args.full and world_env is None and args.gpus == 1 and not args.no_secondary
+            and not os.environ.get("AIMET_BENCH_CHILD")
             and not os.environ.get("AIMET_BENCH_LAUNCH_CHECK")):
         sys.exit(orchestrate(args))
     if os.environ.get("AIMET_BENCH_LAUNCH_CHECK"):
@@ -529,54 +620,14 @@ def main():
     del x
     torch.cuda.empty_cache()
 
-    # compute_encodings wall-clock: the first call (cold: code objects load, pools grow, quantizers
-    # created), the median of --enc-reps calls on fresh quantizers, and the median of --enc-reps
-    # calls that reset and recompute the same quantizers (QuantizationSimModel.compute_encodings on
-    # an existing sim: the headline); the encodings of the last call are used
-    act_enc, w_enc, enc_cold, aq, wq = compute_encodings(acts, weights)
-    fresh, warm = [], []
-    for _ in range(args.enc_reps):
-        del aq, wq
-        act_enc, w_enc, secs, aq, wq = compute_encodings(acts, weights)
-        fresh.append(secs)
-    for _ in range(args.enc_reps):
-        act_enc, w_enc, secs, aq, wq = compute_encodings(acts, weights, (aq, wq))
-        warm.append(secs)
-    enc_resident = sorted(warm)[len(warm) // 2] if warm else enc_cold
-    enc_fresh = sorted(fresh)[len(fresh) // 2] if fresh else enc_cold
-    # the headline: a calibration plan over the sim's quantizers and the resident activations,
-    # prepared once (as the quantizers are created once with the sim), each timed run a reset +
-    # recompute of every quantizer (aimet_amd.calibration.CalibrationPlan). Sharded at N > 1.
-    from aimet_amd.calibration import CalibrationPlan
-    cplan = CalibrationPlan(aq, [t for _, t in acts], wq, [w for _, w in weights])
-    enc_spans, enc_phases = [], []
-    enc_seconds, (a_res, w_res), enc_runs_ms = time_plan(cplan, max(1, args.plan_reps), spans=enc_spans,
-                                                         phases=enc_phases)
-    # the same on quantizers made for the plan alone (a new sim), for comparison
-    nq, nw = make_quantizers(acts, weights)
-    nplan = CalibrationPlan(nq, [t for _, t in acts], nw, [w for _, w in weights])
-    new_spans = []
-    enc_new_s, _, _ = time_plan(nplan, max(1, args.plan_reps), spans=new_spans)
-    nplan.close()
-    del nq, nw
-    plan_act, plan_w = [e for e, _ in a_res], [e for e, _ in w_res]
-    enc_plan_equal = ([e.to_tuple() for e in plan_act] == [e.to_tuple() for e in act_enc] and
-                      [[x.to_tuple() for x in es] for es in plan_w] == [[x.to_tuple() for x in es] for es in w_enc])
-    act_enc, w_enc = plan_act, plan_w
-    enc_exchange = None
-    if args.force_exchange and world == 1:
-        # the sharded calibration's staged form on this rank (stage 1, RCCL MAX, stage 2, RCCL SUM,
-        # stage 4) over a world-size-1 group: the per-rank cost the 1 -> N curve starts from.
-        # Quantizers of their own (the plan binds them to the packed exchange buffers).
-        xq, xw = make_quantizers(acts, weights)
-        xplan = CalibrationPlan(xq, [t for _, t in acts], xw, [w for _, w in weights], force_exchange=True)
-        x_s, (xa, xwr), x_runs = time_plan(xplan, max(1, args.plan_reps))
-        enc_exchange = {"seconds": round(x_s, 4), "dist_backend": dist.get_backend(),
-                        "world_formed": dist.get_world_size(),
-                        "equal_to_headline": [e.to_tuple() for e, _ in xa] == [e.to_tuple() for e in act_enc] and
-                        [[x.to_tuple() for x in es] for es, _ in xwr] == [[x.to_tuple() for x in es] for es in w_enc]}
-        xplan.close()
-        del xq, xw
+    # the step's encodings: one compute_encodings call; --full times that call's forms and the
+    # calibration plan, and uses the encodings of the plan's last run (the same values)
+    cplan = enc = None
+    if args.full:
+        act_enc, w_enc, aq, wq, cplan, enc = compute_encodings_wall_clock(args, world, acts, weights)
+        enc_cold = enc["cold"]
+    else:
+        act_enc, w_enc, enc_cold, aq, wq = compute_encodings(acts, weights)
 
     # ---- the step: every QDQ of one QuantSim forward, pre-bound C-ABI calls --------------------
     stream = torch.cuda.current_stream(dev)
@@ -674,6 +725,13 @@ def main():
     # HIP events on the launch stream bracket the activation QDQ launches of every timed step
     act_ms = [s.elapsed_time(e) for s, e in ev]
     kernel_ms = sum(act_ms) / len(act_ms)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs,
+                     [("act_%02d_%s" % (k, name.replace(".", "_")), o)
+                      for k, ((name, _), o) in enumerate(zip(acts, act_outs))] +
+                     [("weight_%02d_%s" % (k, name.replace(".", "_")), o)
+                      for k, ((name, _), o) in enumerate(zip(weights, outs[0::2]))])
+    enc_seconds, enc_fresh, enc_resident = (enc["seconds"], enc["fresh"], enc["resident"]) if enc else (0.0, 0.0, 0.0)
     if world > 1:
         tt = torch.tensor([dt, enc_seconds, enc_cold, enc_fresh, enc_resident], dtype=torch.float64,
                           device=dev if dist.get_backend() == "nccl" else "cpu")
@@ -701,30 +759,7 @@ def main():
                    "per_gpu_batch": args.batch, "act_elems_per_step": n_act, "weight_elems_per_step": n_w,
                    "act_quantizers": len(act_calls), "weight_quantizers": len(w_calls),
                    "weight_channels": int(sum(c[3] for c in w_calls)), "parallelism": "dp%d" % world,
-                   "compute_encodings_s": round(enc_seconds, 4),
                    "compute_encodings_cold_s": round(enc_cold, 4),
-                   "compute_encodings_fresh_quantizers_s": round(enc_fresh, 4),
-                   "compute_encodings_resident_s": round(enc_resident, 4),
-                   "compute_encodings_runs_ms": enc_runs_ms,
-                   "compute_encodings_gpu_span_ms": enc_spans,
-                   "compute_encodings_host_phases_ms": enc_phases,
-                   "compute_encodings_new_sim_s": round(enc_new_s, 4),
-                   "compute_encodings_new_sim_gpu_span_ms": sorted(new_spans)[len(new_spans) // 2] if new_spans else None,
-                   "compute_encodings_plan_equals_resident": enc_plan_equal,
-                   # two passes (min/max, histogram) of 4 B over every activation and weight element
-                   "compute_encodings_roofline": {
-                       "algorithmic_gb": round(8 * n_step / 1e9, 3),
-                       "achieved_gbps": round(8 * n_step / enc_seconds / 1e9, 1),
-                       "frac": round(8 * n_step / enc_seconds / 1e9 / HBM_PEAK_GBPS, 4)},
-                   "compute_encodings_timing": "median of %d CalibrationPlan.run(reset=True) calls (after 2 "
-                                               "untimed ones): reset and "
-                                               "recompute the sim's quantizers (created once, as QuantizationSimModel "
-                                               "does) with the plan prepared once over the resident activations; "
-                                               "beside it the first call of the process (cold), %d "
-                                               "compute_encodings_resident calls on fresh quantizers (plan made "
-                                               "inside) and %d on the sim's quantizers (cached plan, its tensors "
-                                               "checked by identity every call); max over ranks"
-                                               % (max(1, args.plan_reps), args.enc_reps, args.enc_reps),
                    "compute_encodings_scheme": "tf_enhanced act per-tensor + tf_enhanced weight per-channel sym"},
         "roofline": {"bound": "hbm", "kernel": "qdq_per_tensor (tensor_vec_kernel)",
                      "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -735,7 +770,32 @@ def main():
                      "timing": "HIP events on the launch stream around the %d activation QDQ launches of each "
                                "timed step (%s)" % (len(act_calls), "graph replay" if use_graph else "eager")},
     }
-    if world == 1 and not args.no_dropin:
+    if args.full:
+        result["config"].update({
+            "compute_encodings_s": round(enc_seconds, 4),
+            "compute_encodings_fresh_quantizers_s": round(enc_fresh, 4),
+            "compute_encodings_resident_s": round(enc_resident, 4),
+            "compute_encodings_runs_ms": enc["runs_ms"],
+            "compute_encodings_gpu_span_ms": enc["spans"],
+            "compute_encodings_host_phases_ms": enc["phases"],
+            "compute_encodings_new_sim_s": round(enc["new_s"], 4),
+            "compute_encodings_new_sim_gpu_span_ms": sorted(enc["new_spans"])[len(enc["new_spans"]) // 2] if enc["new_spans"] else None,
+            "compute_encodings_plan_equals_resident": enc["plan_equal"],
+            # two passes (min/max, histogram) of 4 B over every activation and weight element
+            "compute_encodings_roofline": {
+                "algorithmic_gb": round(8 * n_step / 1e9, 3),
+                "achieved_gbps": round(8 * n_step / enc_seconds / 1e9, 1),
+                "frac": round(8 * n_step / enc_seconds / 1e9 / HBM_PEAK_GBPS, 4)},
+            "compute_encodings_timing": "median of %d CalibrationPlan.run(reset=True) calls (after 2 "
+                                        "untimed ones): reset and "
+                                        "recompute the sim's quantizers (created once, as QuantizationSimModel "
+                                        "does) with the plan prepared once over the resident activations; "
+                                        "beside it the first call of the process (cold), %d "
+                                        "compute_encodings_resident calls on fresh quantizers (plan made "
+                                        "inside) and %d on the sim's quantizers (cached plan, its tensors "
+                                        "checked by identity every call); max over ranks"
+                                        % (max(1, args.plan_reps), args.enc_reps, args.enc_reps)})
+    if args.full and world == 1 and not args.no_dropin:
         # the whole step's QDQ kernel time: the activation launches (events) + the weights' launch
         w_ms = []
         for _ in range(5):
@@ -754,7 +814,7 @@ def main():
             result["config"]["dropin"] = {"error": "%s: %s" % (type(e).__name__, e)}
     del model
     cb = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:   # a failure of the host-side baseline is recorded in the line, not fatal to it
             cb = cpu_baseline(acts, weights, act_enc, w_enc, args.cpu_sample_images, act_outs, outs[0::2])
         except Exception as e:   # noqa: BLE001
@@ -779,13 +839,14 @@ def main():
             result["cpu_baseline"] = {"value": port["value"], "unit": "Gelem/s", "cores": 1, "kind": "port",
                                       "sample": sample + "; " + port["what"], "seconds": port["seconds"],
                                       "omp": omp, "parity": cb["parity"], "compute_encodings": cb["enc"]}
+    enc_exchange = enc["exchange"] if enc else None
     if enc_exchange is not None:
         result["config"]["compute_encodings_exchange_s"] = enc_exchange["seconds"]
         result["config"]["compute_encodings_exchange"] = dict(
             enc_exchange, ratio_to_headline=round(enc_exchange["seconds"] / enc_seconds, 4),
             what="the sharded calibration's staged plan (stage 1, all_reduce MAX, stage 2, all_reduce SUM, stage 4) "
                  "over a world-size-1 group formed before any GPU call; median of the same reset+recompute runs")
-    if world > 1:
+    if args.full and world > 1:
         # the calibration exchange of this workload: what formed, and the two collectives' cost
         result["config"]["dist_backend"] = dist.get_backend()
         result["config"]["world_formed"] = dist.get_world_size()
@@ -801,7 +862,8 @@ def main():
         result["config"]["encodings_identical_across_ranks"] = bool(lo.item() == hi.item())
     if rank == 0:
         print(json.dumps(result), flush=True)
-    cplan.close()
+    if cplan is not None:
+        cplan.close()
     if dist.is_initialized():
         dist.destroy_process_group()
 

@@ -19,11 +19,11 @@ run() {  # name timeout cmd...
 }
 case ",$STEPS," in *,smoke,*) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()";; esac
 case ",$STEPS," in *,pytest,*) run pytest_gpu 1200 python -m pytest tests -q -m gpu -p no:cacheprovider;; esac
-case ",$STEPS," in *,bench,*) run bench 600 python bench.py ${BENCH_ARGS:-};; esac
+case ",$STEPS," in *,bench,*) run bench 600 python bench.py --full ${BENCH_ARGS:-};; esac
 export TMPDIR=/tmp
 case ",$STEPS," in *,prof,*)
-  run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline;; esac
+  run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline;; esac
 case ",$STEPS," in *,pmc,*)
-  run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline
-  run pmc_write 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline;; esac
+  run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -o run --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
+  run pmc_write 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -o run --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline;; esac
 echo ALLDONE

@@ -1,7 +1,8 @@
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
-timeout -k 10 900 python -m pytest tests -m gpu -x -q > gpurun_out/gpu_tests.log 2>&1 &&
-timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err &&
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_trace -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/prof_trace.log 2>&1 &&
-timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/gpurun_out/prof_fetch -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/prof_fetch.log 2>&1 &&
-timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $R/gpurun_out/prof_write -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/prof_write.log 2>&1
+OUT=${OUT:-$PWD/check_out}
+mkdir -p "$OUT"
+timeout -k 10 900 python -m pytest tests -m gpu -x -q > "$OUT/gpu_tests.log" 2>&1 &&
+timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" &&
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_trace" -o run -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/prof_trace.log" 2>&1 &&
+timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/prof_fetch" -o run -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/prof_fetch.log" 2>&1 &&
+timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/prof_write" -o run -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/prof_write.log" 2>&1
