@@ -92,6 +92,7 @@ _PROTOTYPES = {
     "aimet_qc_quantize_op_compute": [ctypes.POINTER(QcQuantizeInfoC), _vp, _vp, _i64p, _i64, _vp],
     "aimet_encoding_from_entropy_histogram": [_int, _int, ctypes.c_double, ctypes.c_double, _dp, _i32, _int, _int,
                                               _int, _enc_p],
+    "aimet_qdq_tile_lanes": [_int, ctypes.POINTER(_int)],
     "aimet_qdq_per_tensor": [_vp, _vp, _i64, _enc_p, _int, ctypes.c_uint64, _vp],
     "aimet_quantize_per_tensor": [_vp, _vp, _i64, _enc_p, _int, _int, ctypes.c_uint64, _vp],
     "aimet_per_channel_table": [_enc_p, _i64, _vp, _vp],

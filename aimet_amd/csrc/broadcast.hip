@@ -341,12 +341,16 @@ __device__ __forceinline__ float fp16_rt(float x)
     return (float) (_Float16) x;
 }
 
-// one float4 per lane, one 256-lane tile per workgroup (the tensor_vec_kernel form: 6.4 TB/s
-// where a 2048-workgroup grid-stride loop reached 5.2)
-__global__ __launch_bounds__(kBlock) void fp16_vec_kernel(const f4* __restrict__ in, f4* __restrict__ out,
-                                                          int64_t nvec)
+// one float4 per lane, one LANES-lane tile per workgroup (the tensor_vec_kernel form: 6.4 TB/s at
+// 256 lanes where a 2048-workgroup grid-stride loop reached 5.2). 64 lanes: +2.5 % in the sweep and
+// +2.7 % in benchmarks/kernel_roofline.py, short of three times that row's run-to-run spread, so
+// 256 lanes stays (profiles/r07/qdq_tile_sweep.txt)
+constexpr int kFp16Lanes = 256;
+template <int LANES>
+__global__ __launch_bounds__(LANES) void fp16_vec_kernel(const f4* __restrict__ in, f4* __restrict__ out,
+                                                         int64_t nvec)
 {
-    const int64_t i = (int64_t) blockIdx.x * kBlock + threadIdx.x;
+    const int64_t i = (int64_t) blockIdx.x * LANES + threadIdx.x;
     if (i >= nvec)
         return;
     f4 x = __builtin_nontemporal_load(in + i);
@@ -441,9 +445,11 @@ void launch_qdq_fp16(const float* in, float* out, int64_t n, hipStream_t s)
         int64_t nvec = n / 4;
         if (nvec)
         {
-            AIMET_REQUIRE(ceil_div(nvec, kBlock) < (int64_t(1) << 31), "tensor too large");
-            fp16_vec_kernel<<<(unsigned) ceil_div(nvec, kBlock), kBlock, 0, s>>>(reinterpret_cast<const f4*>(in),
-                                                                               reinterpret_cast<f4*>(out), nvec);
+            with_lanes(tile_lanes(kFp16Lanes), [&](auto L) {
+                constexpr int LANES = decltype(L)::value;
+                fp16_vec_kernel<LANES><<<tile_grid(nvec, LANES), LANES, 0, s>>>(reinterpret_cast<const f4*>(in),
+                                                                              reinterpret_cast<f4*>(out), nvec);
+            });
             AIMET_LAUNCH_CHECK();
         }
         done = nvec * 4;

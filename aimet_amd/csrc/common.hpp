@@ -13,6 +13,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "aimet_amd.h"
 
@@ -110,6 +111,41 @@ inline int stream_blocks(int64_t work_items, int64_t items_per_block)
     if (b > kMaxStreamBlocks)
         b = kMaxStreamBlocks;
     return (int) b;
+}
+
+// ------------------------------------------------------------------------------------------
+// Tile shape of the streaming vector kernels: LANES lanes per workgroup (1, 2 or 4 waves), one
+// tile per workgroup, grid = ceil(items / LANES). A lane's element index (and with it a stochastic
+// draw) does not depend on the shape. Each kernel family has its measured default
+// (tools/studies/qdq_tile_sweep.hip, profiles/r07/qdq_tile_sweep.txt); aimet_qdq_tile_lanes
+// overrides all of them for the study and the tests.
+// ------------------------------------------------------------------------------------------
+int forced_tile_lanes();   // qdq.hip: 0 (the defaults), 64, 128 or 256
+
+inline int tile_lanes(int family_default)
+{
+    int forced = forced_tile_lanes();
+    return forced ? forced : family_default;
+}
+
+// f(std::integral_constant<int, LANES>) for the runtime shape
+template <class F>
+void with_lanes(int lanes, F&& f)
+{
+    switch (lanes)
+    {
+    case 64: f(std::integral_constant<int, 64> {}); break;
+    case 128: f(std::integral_constant<int, 128> {}); break;
+    default: f(std::integral_constant<int, 256> {}); break;
+    }
+}
+
+// workgroups of a one-tile-per-workgroup launch over `items` (the grid's x limit is 2^31 - 1)
+inline unsigned tile_grid(int64_t items, int64_t items_per_block)
+{
+    int64_t blocks = ceil_div(items, items_per_block);
+    AIMET_REQUIRE(blocks < (int64_t(1) << 31), "tensor too large for one launch (>= 2^31 workgroups)");
+    return (unsigned) blocks;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -205,32 +205,37 @@ __device__ __forceinline__ void lg_store4(void* __restrict__ y, uint32_t q, f4 r
     }
 }
 
+// lg_fwd_kernel's lanes per workgroup (common.hpp: tile shapes). 64 lanes: +2.5 % in the sweep,
+// +2.3 % in benchmarks/kernel_roofline.py, short of three times that row's run-to-run spread, so
+// 256 stays (profiles/r07/qdq_tile_sweep.txt)
+constexpr int kLgFwdLanes = 256;
+
 // OUT = IO_F32: y float32. OUT = IO_F16 / IO_BF16: y written in 16 bits with torch's rounding --
 // the float32 result cast as autocast casts a weight for its matmul, fused into the store.
-// Q quads per lane (vec form), kBlock apart: their loads are issued together and a channel's
+// Q quads per lane (vec form), LANES apart: their loads are issued together and a channel's
 // encoding is computed once for consecutive quads of that channel (quad q with q * 4 == c * K
 // is never preceded by a quad of channel c, so the store of the first one still happens)
-template <int OUT, int Q>
-__global__ __launch_bounds__(kBlock) void lg_fwd_kernel(const float* __restrict__ x, void* __restrict__ y,
-                                                        uint32_t n, LgChannel map, const float* __restrict__ delta,
-                                                        const float* __restrict__ offset, float steps, int vec,
-                                                        LgEnc enc)
+template <int LANES, int OUT, int Q>
+__global__ __launch_bounds__(LANES) void lg_fwd_kernel(const float* __restrict__ x, void* __restrict__ y,
+                                                       uint32_t n, LgChannel map, const float* __restrict__ delta,
+                                                       const float* __restrict__ offset, float steps, int vec,
+                                                       LgEnc enc)
 {
     if (vec)
     {
         const uint32_t nq = n / 4;
-        const uint32_t q0 = blockIdx.x * (kBlock * Q) + threadIdx.x;
+        const uint32_t q0 = blockIdx.x * (LANES * Q) + threadIdx.x;
         f4 v[Q];
 #pragma unroll
         for (int u = 0; u < Q; ++u)
-            if (q0 + u * kBlock < nq)
-                v[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(x) + q0 + u * kBlock);
+            if (q0 + u * LANES < nq)
+                v[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(x) + q0 + u * LANES);
         uint32_t pc = 0xffffffffu;
         float d = 0.0f, o = 0.0f, rd = 0.0f;
 #pragma unroll
         for (int u = 0; u < Q; ++u)
         {
-            const uint32_t q = q0 + u * kBlock;
+            const uint32_t q = q0 + u * LANES;
             if (q >= nq)
                 return;
             const uint32_t c = map.channel(q * 4);
@@ -249,7 +254,7 @@ __global__ __launch_bounds__(kBlock) void lg_fwd_kernel(const float* __restrict_
     }
     else
     {
-        const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+        const uint32_t t = blockIdx.x * LANES + threadIdx.x;
         if (t >= n)
             return;
         uint32_t c = map.channel(t);
@@ -269,12 +274,15 @@ void launch_lg_fwd(const float* x, void* y, int64_t n, LgChannel map, const floa
 {
     // two quads per lane in the vec form (one: 4.4 vs 5.4 TB/s on the Llama-3-8B weights; four: no
     // faster, profiles/r02/llama_qat_kernel_stats*.csv)
-    if (vec)
-        lg_fwd_kernel<OUT, 2><<<(unsigned) ceil_div(n / 4, kBlock * 2), kBlock, 0, st>>>(x, y, (uint32_t) n, map, delta,
-                                                                                       offset, steps, 1, enc);
-    else
-        lg_fwd_kernel<OUT, 1><<<(unsigned) ceil_div(vec ? n / 4 : n, kBlock), kBlock, 0, st>>>(
-            x, y, (uint32_t) n, map, delta, offset, steps, vec ? 1 : 0, enc);
+    with_lanes(tile_lanes(kLgFwdLanes), [&](auto L) {
+        constexpr int LANES = decltype(L)::value;
+        if (vec)
+            lg_fwd_kernel<LANES, OUT, 2><<<tile_grid(n / 4, LANES * 2), LANES, 0, st>>>(x, y, (uint32_t) n, map, delta,
+                                                                                      offset, steps, 1, enc);
+        else
+            lg_fwd_kernel<LANES, OUT, 1><<<tile_grid(n, LANES), LANES, 0, st>>>(x, y, (uint32_t) n, map, delta, offset,
+                                                                              steps, 0, enc);
+    });
     AIMET_LAUNCH_CHECK();
 }
 

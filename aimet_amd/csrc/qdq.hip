@@ -6,12 +6,24 @@
 // common.hpp measures 4% slower here -- this kernel is HBM-bound, the fast path's extra VGPRs and
 // branch cost more than the division; it pays off in the 16-bit and histogram kernels).
 // MI355X design: HBM-bound streaming (8 B/elem fwd, 12 B/elem STE) -> one 16-B vector per lane,
-// one tile per 256-thread workgroup (thousands of workgroups fill the 256 CUs), non-temporal
-// loads/stores (streamed once, kept out of L2/MALL), scalar encoding parameters in SGPRs,
-// per-channel parameters fetched once per 16-B vector (K % 4 == 0) from a device-resident table
-// built once per encoding.
+// one tile per single-wave (64-lane) workgroup (STE: 256), non-temporal loads/stores (streamed once, kept out
+// of L2/MALL), scalar encoding parameters in SGPRs, per-channel parameters fetched once per 16-B
+// vector (K % 4 == 0) from a device-resident table built once per encoding.
+// The tile shape is a template parameter (64 / 128 / 256 lanes), chosen from a sweep through the
+// library itself, back-to-back launches from a HIP graph over fresh memory
+// (tools/studies/qdq_tile_sweep.hip, profiles/r07/qdq_tile_sweep.txt), 64 / 128 / 256 lanes:
+//   per-tensor, 6.4 M elements      5.28 / 5.04 / 5.12 TB/s     205.5 M      6.77 / 6.60 / 6.56 TB/s
+//   the flagship step's 53 launches of its six sizes, byte-weighted: 6.63 / 6.42 / 6.38 TB/s
+//   per-channel 256x64x12544        6.75 / 6.47 / 6.45 TB/s     STE 205.5 M  6.59 / 6.49 / 6.42 TB/s
+//   batched plan, 54 ResNet-50 weights (25.5 M elements): 6.11 / 5.64 / 5.74 TB/s
+// One wave per workgroup wins at every size and 128 lanes is within 1 % of 256, so there is no
+// size threshold; the flagship step went from 3.594 to 3.456 ms of tensor_vec_kernel time
+// (rocprofv3), 796.0 -> 829.0 Gelem/s. Adopted where the gain cleared three times the parent's
+// run-to-run spread: per-tensor and batched (bench.py), per-channel (benchmarks/kernel_roofline.py:
+// 6.46 -> 6.74 TB/s). The STE kernels' +3.4 % there fell just short, so they stay at 256 lanes.
 #include "common.hpp"
 
+#include <atomic>
 #include <cmath>
 #include <vector>
 
@@ -39,9 +51,9 @@ __device__ __forceinline__ float apply(float x, const QdqParams& p, float shift,
 
 // ---------------------------------------------------------------------------------------
 // Per-tensor: parameters are kernel arguments (SGPRs). One 16-B vector per lane, one tile per
-// workgroup, non-temporal (streaming) loads and stores: measured on MI355X at 6.6 TB/s for a
-// 2 GiB in+out stream vs 5.6 TB/s for a grid-strided 4-vector loop with default cache policy
-// (tools/studies/qdq_variants.hip, profiles/r01/qdq_variants.txt).
+// workgroup, non-temporal (streaming) loads and stores: 6.80 TB/s for a 2 GiB in+out stream at
+// 64 lanes (6.59 at 256; a grid-strided 4-vector loop with default cache policy reached 5.6:
+// tools/studies/qdq_variants.hip, profiles/r01/qdq_variants.txt).
 // ---------------------------------------------------------------------------------------
 typedef float f4 __attribute__((ext_vector_type(4)));
 
@@ -54,11 +66,19 @@ __device__ __forceinline__ void store_stream(f4 v, f4* p)
     __builtin_nontemporal_store(v, p);
 }
 
-template <Op OP, bool STOCHASTIC>
-__global__ __launch_bounds__(kBlock) void tensor_vec_kernel(const f4* __restrict__ in, f4* __restrict__ out,
-                                                            int64_t nvec, QdqParams p, float shift, uint64_t seed)
+// Tile shapes (common.hpp: tile_lanes / with_lanes / tile_grid), one 16-B vector per lane
+constexpr int kTensorLanes  = 64;    // tensor_vec_kernel
+constexpr int kChannelLanes = 64;    // channel_vec_kernel
+constexpr int kBatchLanes   = 64;    // channel_batch_kernel (fixed per plan at its creation)
+constexpr int kSteLanes     = 256;   // ste_*_vec_kernel (64: +3.4 % in kernel_roofline.py, short of the margin)
+
+std::atomic<int> g_tile_lanes {0};   // aimet_qdq_tile_lanes; 0: the defaults above
+
+template <int LANES, Op OP, bool STOCHASTIC>
+__global__ __launch_bounds__(LANES) void tensor_vec_kernel(const f4* __restrict__ in, f4* __restrict__ out,
+                                                           int64_t nvec, QdqParams p, float shift, uint64_t seed)
 {
-    const int64_t i = (int64_t) blockIdx.x * kBlock + threadIdx.x;
+    const int64_t i = (int64_t) blockIdx.x * LANES + threadIdx.x;
     if (i >= nvec)
         return;
     f4 v = load_stream(in + i);
@@ -91,10 +111,11 @@ void launch_tensor(const float* in, float* out, int64_t n, const QdqParams& p, f
     int64_t nvec = aligned ? n / 4 : 0;
     if (nvec > 0)
     {
-        int64_t blocks = ceil_div(nvec, kBlock);
-        tensor_vec_kernel<OP, STOCHASTIC><<<(unsigned) blocks, kBlock, 0, s>>>(reinterpret_cast<const f4*>(in),
-                                                                                reinterpret_cast<f4*>(out), nvec, p,
-                                                                                shift, seed);
+        with_lanes(tile_lanes(kTensorLanes), [&](auto L) {
+            constexpr int LANES = decltype(L)::value;
+            tensor_vec_kernel<LANES, OP, STOCHASTIC><<<tile_grid(nvec, LANES), LANES, 0, s>>>(
+                reinterpret_cast<const f4*>(in), reinterpret_cast<f4*>(out), nvec, p, shift, seed);
+        });
         AIMET_LAUNCH_CHECK();
     }
     int64_t done = nvec * 4;
@@ -127,12 +148,12 @@ __device__ __forceinline__ QdqParams load_params(const float* __restrict__ table
 }
 
 // K % 4 == 0: a 16-B vector never straddles two channels.
-template <bool STOCHASTIC>
-__global__ __launch_bounds__(kBlock) void channel_vec_kernel(const f4* __restrict__ in, f4* __restrict__ out,
-                                                             uint32_t nvec, ChannelMap map,
-                                                             const float* __restrict__ table, uint64_t seed)
+template <int LANES, bool STOCHASTIC>
+__global__ __launch_bounds__(LANES) void channel_vec_kernel(const f4* __restrict__ in, f4* __restrict__ out,
+                                                            uint32_t nvec, ChannelMap map,
+                                                            const float* __restrict__ table, uint64_t seed)
 {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t i = blockIdx.x * LANES + threadIdx.x;
     if (i >= nvec)
         return;
     f4 v        = load_stream(in + i);
@@ -183,10 +204,11 @@ __device__ __forceinline__ float ste(float x, float g, float mn, float mx)
     return g * ((mn <= x && x <= mx) ? 1.0f : 0.0f);
 }
 
-__global__ __launch_bounds__(kBlock) void ste_tensor_vec_kernel(const f4* __restrict__ x, const f4* __restrict__ g,
-                                                                f4* __restrict__ gi, int64_t nvec, float mn, float mx)
+template <int LANES>
+__global__ __launch_bounds__(LANES) void ste_tensor_vec_kernel(const f4* __restrict__ x, const f4* __restrict__ g,
+                                                               f4* __restrict__ gi, int64_t nvec, float mn, float mx)
 {
-    const int64_t i = (int64_t) blockIdx.x * kBlock + threadIdx.x;
+    const int64_t i = (int64_t) blockIdx.x * LANES + threadIdx.x;
     if (i >= nvec)
         return;
     f4 a = load_stream(x + i), b = load_stream(g + i), r;
@@ -217,12 +239,13 @@ __global__ __launch_bounds__(kBlock) void ste_scalar_kernel(const float* __restr
     }
 }
 
-__global__ __launch_bounds__(kBlock) void ste_channel_vec_kernel(const f4* __restrict__ x, const f4* __restrict__ g,
-                                                                 f4* __restrict__ gi, uint32_t nvec, ChannelMap map,
-                                                                 const float* __restrict__ mins,
-                                                                 const float* __restrict__ maxs)
+template <int LANES>
+__global__ __launch_bounds__(LANES) void ste_channel_vec_kernel(const f4* __restrict__ x, const f4* __restrict__ g,
+                                                                f4* __restrict__ gi, uint32_t nvec, ChannelMap map,
+                                                                const float* __restrict__ mins,
+                                                                const float* __restrict__ maxs)
 {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t i = blockIdx.x * LANES + threadIdx.x;
     if (i >= nvec)
         return;
     uint32_t c = map.channel(i * 4);
@@ -246,13 +269,13 @@ struct BatchDesc
     ChannelMap map;
     uint32_t n;           // elements
     uint32_t vec;         // 16-B vector path (K % 4 == 0, aligned)
-    uint32_t block0;      // first workgroup of this tensor in the flattened grid
+    uint32_t block0;      // first workgroup of this tensor in the flattened grid (of the plan's tile shape)
     uint32_t pad;
 };
 
-template <bool STOCHASTIC>
-__global__ __launch_bounds__(kBlock) void channel_batch_kernel(const BatchDesc* __restrict__ descs, int count,
-                                                               uint64_t seed)
+template <int LANES, bool STOCHASTIC>
+__global__ __launch_bounds__(LANES) void channel_batch_kernel(const BatchDesc* __restrict__ descs, int count,
+                                                              uint64_t seed)
 {
     // find the tensor of this workgroup (block0 is increasing): scalar binary search
     int lo = 0, hi = count - 1;
@@ -266,7 +289,7 @@ __global__ __launch_bounds__(kBlock) void channel_batch_kernel(const BatchDesc* 
             hi = mid - 1;
     }
     const BatchDesc& d = descs[lo];
-    const uint32_t t   = (b - d.block0) * kBlock + threadIdx.x;
+    const uint32_t t   = (b - d.block0) * LANES + threadIdx.x;
     if (d.vec)
     {
         if (t >= d.n / 4)
@@ -305,6 +328,11 @@ aimet_tf_encoding fill_encoding_info(int32_t bw, double mn, double mx);   // enc
 
 void per_channel_table_host(const aimet_tf_encoding* encs, int64_t C, float* table);   // encodings.cpp
 
+int forced_tile_lanes()
+{
+    return g_tile_lanes.load(std::memory_order_relaxed);
+}
+
 QdqParams tensor_params(const aimet_tf_encoding& enc)
 {
     aimet_tf_encoding e = fill_encoding_info(enc.bw, enc.min, enc.max);
@@ -319,6 +347,7 @@ struct aimet_qdq_plan
 {
     int device          = 0;
     int count           = 0;
+    int lanes           = 0;         // tile shape of block0 / blocks, fixed at creation
     uint32_t blocks     = 0;
     BatchDesc* descs    = nullptr;   // device
 };
@@ -331,6 +360,7 @@ int aimet_qdq_channel_plan_create(const aimet_qdq_channel_desc* descs, int64_t c
         AIMET_REQUIRE(out != nullptr && descs != nullptr && count > 0, "empty plan");
         AIMET_REQUIRE(count < (1 << 20), "too many tensors in one plan");
         std::vector<BatchDesc> h((size_t) count);
+        const int lanes = tile_lanes(kBatchLanes);
         uint64_t blocks = 0;
         for (int64_t i = 0; i < count; ++i)
         {
@@ -353,12 +383,13 @@ int aimet_qdq_channel_plan_create(const aimet_qdq_channel_desc* descs, int64_t c
             b.vec        = (d.K % 4 == 0 && aligned16(d.in, d.out)) ? 1u : 0u;
             b.block0     = (uint32_t) blocks;
             b.pad        = 0;
-            blocks += (uint64_t) ceil_div(b.vec ? n / 4 : n, kBlock);
+            blocks += (uint64_t) ceil_div(b.vec ? n / 4 : n, lanes);
         }
         AIMET_REQUIRE(blocks < (uint64_t(1) << 31), "plan too large");
         auto* plan   = new aimet_qdq_plan();
         plan->device = device;
         plan->count  = (int) count;
+        plan->lanes  = lanes;
         plan->blocks = (uint32_t) blocks;
         int prev     = 0;
         AIMET_HIP_CHECK(hipGetDevice(&prev));
@@ -387,10 +418,13 @@ int aimet_qdq_channel_plan_run(aimet_qdq_plan* plan, int round_mode, uint64_t se
         if (plan->blocks == 0)
             return;
         hipStream_t s = as_stream(stream);
-        if (round_mode == AIMET_ROUND_STOCHASTIC)
-            channel_batch_kernel<true><<<plan->blocks, kBlock, 0, s>>>(plan->descs, plan->count, seed);
-        else
-            channel_batch_kernel<false><<<plan->blocks, kBlock, 0, s>>>(plan->descs, plan->count, seed);
+        with_lanes(plan->lanes, [&](auto L) {
+            constexpr int LANES = decltype(L)::value;
+            if (round_mode == AIMET_ROUND_STOCHASTIC)
+                channel_batch_kernel<LANES, true><<<plan->blocks, LANES, 0, s>>>(plan->descs, plan->count, seed);
+            else
+                channel_batch_kernel<LANES, false><<<plan->blocks, LANES, 0, s>>>(plan->descs, plan->count, seed);
+        });
         AIMET_LAUNCH_CHECK();
     });
 }
@@ -406,6 +440,16 @@ int aimet_qdq_channel_plan_destroy(aimet_qdq_plan* plan)
             AIMET_HIP_CHECK(hipFree(plan->descs));
         }
         delete plan;
+    });
+}
+
+int aimet_qdq_tile_lanes(int lanes, int* previous)
+{
+    return guarded([&] {
+        AIMET_REQUIRE(lanes == 0 || lanes == 64 || lanes == 128 || lanes == 256, "tile lanes: 0, 64, 128 or 256");
+        int prev = g_tile_lanes.exchange(lanes, std::memory_order_relaxed);
+        if (previous)
+            *previous = prev;
     });
 }
 
@@ -511,15 +555,16 @@ int aimet_qdq_per_channel(const float* in, float* out, int64_t outer, int64_t C,
         if (K % 4 == 0 && aligned16(in, out))
         {
             uint32_t nvec = (uint32_t) (n / 4);
-            unsigned blocks = (unsigned) ceil_div(nvec, kBlock);
-            if (sto)
-                channel_vec_kernel<true><<<blocks, kBlock, 0, s>>>(reinterpret_cast<const f4*>(in),
-                                                                    reinterpret_cast<f4*>(out), nvec, map, table,
-                                                                    seed);
-            else
-                channel_vec_kernel<false><<<blocks, kBlock, 0, s>>>(reinterpret_cast<const f4*>(in),
-                                                                     reinterpret_cast<f4*>(out), nvec, map, table,
-                                                                     seed);
+            with_lanes(tile_lanes(kChannelLanes), [&](auto L) {
+                constexpr int LANES = decltype(L)::value;
+                const unsigned blocks = tile_grid(nvec, LANES);
+                if (sto)
+                    channel_vec_kernel<LANES, true><<<blocks, LANES, 0, s>>>(
+                        reinterpret_cast<const f4*>(in), reinterpret_cast<f4*>(out), nvec, map, table, seed);
+                else
+                    channel_vec_kernel<LANES, false><<<blocks, LANES, 0, s>>>(
+                        reinterpret_cast<const f4*>(in), reinterpret_cast<f4*>(out), nvec, map, table, seed);
+            });
         }
         else
         {
@@ -547,9 +592,12 @@ int aimet_ste_backward_per_tensor(const float* x, const float* g, float* gi, int
         int64_t nvec  = aligned16(x, g, gi) ? n / 4 : 0;
         if (nvec > 0)
         {
-            ste_tensor_vec_kernel<<<(unsigned) ceil_div(nvec, kBlock), kBlock, 0, s>>>(
-                reinterpret_cast<const f4*>(x), reinterpret_cast<const f4*>(g), reinterpret_cast<f4*>(gi), nvec, mn,
-                mx);
+            with_lanes(tile_lanes(kSteLanes), [&](auto L) {
+                constexpr int LANES = decltype(L)::value;
+                ste_tensor_vec_kernel<LANES><<<tile_grid(nvec, LANES), LANES, 0, s>>>(
+                    reinterpret_cast<const f4*>(x), reinterpret_cast<const f4*>(g), reinterpret_cast<f4*>(gi), nvec,
+                    mn, mx);
+            });
             AIMET_LAUNCH_CHECK();
         }
         if (nvec * 4 < n)
@@ -579,9 +627,12 @@ int aimet_ste_backward(const float* x, const float* g, float* gi, int64_t outer,
         {
             ChannelMap map {FastDiv((uint32_t) K), FastDiv((uint32_t) C), (uint32_t) C};
             uint32_t nvec = (uint32_t) (n / 4);
-            ste_channel_vec_kernel<<<(unsigned) ceil_div(nvec, kBlock), kBlock, 0, s>>>(
-                reinterpret_cast<const f4*>(x), reinterpret_cast<const f4*>(g), reinterpret_cast<f4*>(gi), nvec, map,
-                mins, maxs);
+            with_lanes(tile_lanes(kSteLanes), [&](auto L) {
+                constexpr int LANES = decltype(L)::value;
+                ste_channel_vec_kernel<LANES><<<tile_grid(nvec, LANES), LANES, 0, s>>>(
+                    reinterpret_cast<const f4*>(x), reinterpret_cast<const f4*>(g), reinterpret_cast<f4*>(gi), nvec,
+                    map, mins, maxs);
+            });
         }
         else
         {

@@ -106,6 +106,12 @@ int aimet_encoding_from_entropy_histogram(int has_histogram, int stats_updated, 
 /* Quantize-dequantize kernels                                                                 */
 /* ------------------------------------------------------------------------------------------ */
 
+/* Lanes per workgroup (64, 128 or 256) of the streaming fp32 vector kernels below (per-tensor,
+ * per-channel, batched plan, STE backward); 0 restores each kernel's measured default. Process-wide;
+ * a batched plan keeps the shape it was created with. *previous (may be NULL) = the value before.
+ * Results do not depend on it: for the tile-shape study and the tests. */
+int aimet_qdq_tile_lanes(int lanes, int* previous);
+
 /* AimetTensorQuantizer.cpp:129-155 quantizeDequantize -> TensorQuantizationSim.cpp:96-114 ->
  * trim_functions.cu:46-60. Uses enc->min/max/bw only (fillEncodingInfo is applied here).
  * `seed` is used by AIMET_ROUND_STOCHASTIC only. in == out is allowed. */
