@@ -197,6 +197,10 @@ _PROTOTYPES = {
     "aimet_adaround_adam_bias_corrections": [ctypes.c_double, ctypes.c_double, _i64, _vp, _vp],
     "aimet_adaround_set_exact_pow": [_int],
     "aimet_adaround_get_exact_pow": [ctypes.POINTER(_int)],
+    "aimet_seqmse_candidate_tables": [_vp, _vp, _i64, _i32, _i32, _int, _int, _int, _vp, _vp],
+    "aimet_seqmse_candidate_qdq": [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp],
+    "aimet_seqmse_recon_sums_workspace": [_i64, _i64, _i64, _i64, _i64p],
+    "aimet_seqmse_recon_sums": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp],
 }
 _RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p}
 

@@ -665,6 +665,40 @@ typedef struct aimet_qc_quantize_info {
 int aimet_qc_quantize_op_compute(aimet_qc_quantize_info* info, const float* in, float* out, const int64_t* shape,
                                  int64_t ndims, void* stream);
 
+/* ---- Sequential MSE (aimet_torch/v1/seq_mse.py:467-503 SequentialMse.optimize_module) ----------
+ * The per-candidate loop of the weight-range grid search as three launches on `stream`. */
+enum aimet_seqmse_loss { AIMET_SEQMSE_LOSS_MSE = 0, AIMET_SEQMSE_LOSS_L1 = 1, AIMET_SEQMSE_LOSS_SQNR = 2 };
+
+/* seq_mse.py:441-464 get_candidates + :505-519 compute_param_encodings for every candidate at
+ * once. From per-channel max_dev[C] (and min_dev[C]; NULL for a symmetric quantizer, where
+ * cand_min = -cand_max) candidate j is max / num_candidates * (j + 1) in fp32 (IEEE divide, then
+ * multiply). tables_dev [num_candidates][4][C] = {min, max, delta, offset}: row j holds the bits
+ * that a TF quantizer fed {cand_min, cand_max}, aimet_tq_get_encoding and aimet_per_channel_table
+ * give for candidate j (the strict-symmetric step count taken from channel 0, as there). Built on
+ * the device, one lane per (candidate, channel), in double; no host synchronisation. */
+int aimet_seqmse_candidate_tables(const float* min_dev, const float* max_dev, int64_t C, int32_t num_candidates,
+                                  int32_t bw, int sym, int strict, int unsign, float* tables_dev, void* stream);
+
+/* seq_mse.py:591-594 _get_quantized_weight for the candidates [first, first + count) in one pass
+ * over w [C][K]: out [count][C][K], nearest rounding, the element arithmetic of
+ * aimet_qdq_per_channel. w is read once (4 + 4 * count bytes per element). C * K < 2^31. */
+int aimet_seqmse_candidate_qdq(const float* w, float* out, int64_t C, int64_t K, const float* tables_dev,
+                               int64_t num_candidates, int64_t first, int64_t count, void* stream);
+
+/* Bytes of workspace aimet_seqmse_recon_sums needs for these sizes. */
+int aimet_seqmse_recon_sums_workspace(int64_t outer, int64_t C, int64_t inner, int64_t count, int64_t* bytes);
+
+/* seq_mse.py:557-581 compute_recon_loss for `count` candidates at once. xw [outer][C][inner] is the
+ * FP32 output, xqwq [outer][count * C][inner] the output against the stacked candidate weights
+ * (channel j * C + c: candidate j, output channel c). inner == 1 is a Linear's [tokens][C]; inner > 1
+ * is a Conv2d's NCHW output as it is. err [count][C] = sum over outer and inner of (xqwq - xw)^2
+ * (MSE, SQNR) or |xqwq - xw| (L1); for SQNR also sig [C] = sum xw^2 (sig may be NULL otherwise).
+ * fp32 accumulation, no atomics: per-workgroup partials in `workspace`, added in a fixed order by
+ * a second pass, so equal inputs give equal bits. count * C < 2^31. */
+int aimet_seqmse_recon_sums(const float* xw, const float* xqwq, int64_t outer, int64_t C, int64_t inner,
+                            int64_t count, int loss_kind, float* err, float* sig, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
