@@ -201,6 +201,12 @@ _PROTOTYPES = {
     "aimet_seqmse_candidate_qdq": [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp],
     "aimet_seqmse_recon_sums_workspace": [_i64, _i64, _i64, _i64, _i64p],
     "aimet_seqmse_recon_sums": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp],
+    "aimet_fp8_scale_table": [_vp, _i64, _int, _vp, _vp],
+    "aimet_fp8_qdq": [_vp, _vp, _i64, _i64, _i64, _vp, _int, _vp],
+    "aimet_fp8_search_workspace": [_i64, _i64, _i64, _i64p],
+    "aimet_fp8_absmax": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp],
+    "aimet_fp8_search_elems": [_int, ctypes.POINTER(_int)],
+    "aimet_fp8_mse_search": [_vp, _i64, _i64, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
 }
 _RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p}
 

@@ -276,7 +276,16 @@ class QcQuantizeWrapper(nn.Module):
                  num_outputs=1, data_type: QuantizationDataType = QuantizationDataType.int):
         super().__init__()
         if data_type == QuantizationDataType.float:
-            raise NotImplementedError("float (fp8/fp16) quantization is outside the MI355X integer QDQ core")
+            # v1/qc_quantize_op.py:221-226; the learned-grid quantizers stay integer only
+            if quant_scheme in (QuantScheme.training_range_learning_with_tf_init,
+                                QuantScheme.training_range_learning_with_tf_enhanced_init):
+                raise NotImplementedError("float (fp8/fp16) quantization is outside the MI355X integer QDQ core")
+            if weight_bw not in (8, 16, 32):
+                raise ValueError("weight_bw in [8, 16, 32] is the only supported configuration with floating "
+                                 "point data type")
+            if activation_bw not in (8, 16, 32):
+                raise ValueError("activation_bw in [8, 16, 32] is the only supported configuration with floating "
+                                 "point data type")
         self.output_quantizers = [tensor_quantizer_factory(activation_bw, round_mode, quant_scheme, is_symmetric,
                                                            enabled_by_default=is_output_quantized,
                                                            data_type=data_type) for _ in range(num_outputs)]
@@ -397,7 +406,9 @@ class QcQuantizeWrapper(nn.Module):
                                        "configuration as the quantsim which was used to export the encodings")
                 continue
             per_channel = isinstance(q, StaticGridPerChannelQuantizer)
-            if isinstance(q, LearnedGridTensorQuantizer):
+            if encoding[0]["dtype"] == "float":
+                pass   # {"bitwidth", "dtype"} only (one entry, whatever the channel count): the quantizer stays
+            elif isinstance(q, LearnedGridTensorQuantizer):
                 pass   # the range parameters take the encoding's channel count
             elif per_channel and q._num_channels != len(encoding):
                 if len(encoding) != 1:
@@ -572,9 +583,12 @@ class StaticGridQuantWrapper(QcQuantizeWrapper):
                 if cache is None:
                     param.data = q.quantize_dequantize(param.data, round_mode)
                     continue
-                # TfEncoding._version moves whenever any encoding is created or assigned
+                # TfEncoding._version moves whenever any encoding is created or assigned; a float / 8
+                # quantizer casts with fp8_maxval, so a changed one is a changed encoding
+                mv = getattr(q, "fp8_maxval", None)
                 key = (param.data_ptr(), param._version, tuple(param.shape), param.dtype, id(q._encoding),
-                       TfEncoding._version, int(round_mode))
+                       TfEncoding._version, int(round_mode), q.data_type, q.bitwidth, id(mv),
+                       None if mv is None else mv._version)
                 out = cache.get(self, name, key)
                 if out is None:
                     out = q.quantize_dequantize(param.data, round_mode)

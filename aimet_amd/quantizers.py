@@ -39,6 +39,9 @@ class QuantizationDataType(enum.Enum):
     float = 2
 
 
+# after QuantScheme: fp_quantization imports it from this (then partly initialised) module
+from aimet_amd import fp_quantization as _fp8   # noqa: E402
+
 MAP_QUANT_SCHEME_TO_PYMO = {   # aimet_common/defs.py:70-78
     QuantScheme.post_training_tf: QuantizationMode.QUANTIZATION_TF,
     QuantScheme.post_training_tf_enhanced: QuantizationMode.QUANTIZATION_TF_ENHANCED,
@@ -65,6 +68,8 @@ def _round_mode(rm):
 class StaticGridTensorQuantizer:
     """v1/tensor_quantizer.py:132-401."""
 
+    fp8_maxval = None   # quantizers pickled before the attribute existed
+
     def __init__(self, bitwidth, round_mode, quant_scheme, use_symmetric_encodings, enabled_by_default,
                  data_type=QuantizationDataType.int):
         self.round_mode = _round_mode(round_mode)
@@ -81,6 +86,7 @@ class StaticGridTensorQuantizer:
         self._is_encoding_frozen = False
         self._encoding = None
         self._cppOp = None
+        self.fp8_maxval = None   # float / 8: the running maximum (a float32 HIP tensor)
 
     def __str__(self):
         s = io.StringIO()
@@ -130,6 +136,7 @@ class StaticGridTensorQuantizer:
         state = self.__dict__.copy()
         state.pop("_cppOp", None)
         state.pop("_ste_cache", None)
+        state.pop("_fp8_table", None)
         encodings = state.pop("_encoding", None)
         state["_pickled_encodings"] = [e.to_tuple() for e in encodings] if encodings else None
         return state
@@ -194,6 +201,7 @@ class StaticGridTensorQuantizer:
         if not self._is_encoding_frozen:
             self._op().resetEncodingStats()
             self._encoding = None
+            self.fp8_maxval = None   # the next batch is a first batch again (the reference keeps the old value)
 
     def get_stats_histogram(self):
         if self._quant_scheme != QuantScheme.post_training_tf_enhanced:
@@ -210,6 +218,40 @@ class StaticGridTensorQuantizer:
 
     def set_percentile_value(self, percentile_value):
         self._op().setPercentileValue(percentile_value)
+
+    def update_maxval(self, maxval):
+        """v1/tensor_quantizer.py:393-400: the first batch's value, then 0.9 * old + 0.1 * new."""
+        if self.fp8_maxval is None:
+            self.fp8_maxval = maxval
+        else:
+            self.fp8_maxval = 0.9 * self.fp8_maxval + 0.1 * maxval.to(self.fp8_maxval.device)
+
+    def _update_fp8_stats(self, tensor, per_channel):
+        """The float branch of update_encoding_stats (v1/tensor_quantizer.py:461-468, 544-552):
+        fp16 is skipped; for 8 bits the scheme's range setting runs on the device, the running
+        fp8_maxval moves, and the encodings carry +-fp8_maxval."""
+        if self.bitwidth != 8:
+            return
+        self.update_maxval(_fp8.INIT_MAP[self.quant_scheme](tensor, self, per_channel))
+        encodings = []
+        for mx in self.fp8_maxval.reshape(-1).tolist():
+            e = TfEncoding()
+            e.max = mx
+            e.min = -mx
+            encodings.append(e)
+        self.encoding = encodings if per_channel else encodings[0]
+
+    def fp8_table(self, device, mantissa_bits):
+        """The QDQ kernel's {maxval, alpha} table, rebuilt on the device (one small launch, no
+        read-back) whenever fp8_maxval or the mantissa width changes."""
+        mv = self.fp8_maxval
+        key = (id(mv), mv._version, int(mantissa_bits), str(device))
+        hit = self.__dict__.get("_fp8_table")
+        if hit is None or hit[0] != key:
+            with torch.cuda.device(device):
+                table = _fp8.scale_table(mv.to(device), mantissa_bits)
+            self.__dict__["_fp8_table"] = hit = (key, table, mv)   # mv: keeps id(mv) from being reused
+        return hit[1]
 
     def _op(self) -> AimetTensorQuantizer:
         return self._cppOp[0]
@@ -244,7 +286,8 @@ class StaticGridPerTensorQuantizer(StaticGridTensorQuantizer):
         if not self.enabled or self._is_encoding_frozen or self.bitwidth == 32:
             return
         if self.data_type == QuantizationDataType.float:
-            raise NotImplementedError("float (fp8/fp16) quantization is outside the MI355X integer QDQ core")
+            self._update_fp8_stats(tensor, False)
+            return
         if self.encoding_min_max_fixed_vals is not None:
             tensor = torch.tensor(list(self.encoding_min_max_fixed_vals), device=tensor.device)
         if tensor.dtype in (torch.float16, torch.bfloat16):
@@ -289,7 +332,8 @@ class StaticGridPerChannelQuantizer(StaticGridTensorQuantizer):
         if not self.enabled or self._is_encoding_frozen or self.bitwidth == 32:
             return
         if self.data_type == QuantizationDataType.float:
-            raise NotImplementedError("float (fp8/fp16) quantization is outside the MI355X integer QDQ core")
+            self._update_fp8_stats(tensor, True)
+            return
         if tensor.dtype in (torch.float16, torch.bfloat16):
             tensor = tensor.to(torch.float32)
         if self.encoding_min_max_fixed_vals is not None:
@@ -410,7 +454,9 @@ def _qdq_values(tensor, tq, round_mode):
     if tq.data_type == QuantizationDataType.float:
         if tq.bitwidth == 16:
             return tensor.half().float()
-        raise NotImplementedError("fp8 quantization is outside the MI355X integer QDQ core")
+        if tq.bitwidth != 8:
+            raise ValueError("float data_type only supports bitwidth in {16, 8}")
+        return _fp8_values(tensor, tq)
     dtype = tensor.dtype
     # a CPU tensor is staged through HBM (the same kernels; the result goes back to the host)
     if tensor.is_cuda:
@@ -428,6 +474,30 @@ def _qdq_values(tensor, tq, round_mode):
     else:
         out = AimetTensorQuantizer.quantize_dequantize_tensor(t, tq.encoding, round_mode)
     return out.to(dtype).cpu() if staged else out.to(dtype)
+
+
+def _fp8_values(tensor, tq):
+    """fp8_quantizer (aimet_torch/fp_quantization.py:127-137) through the FP8 QDQ kernel, with the
+    quantizer's cached scale table; fp16 / bf16 are upcast around it, a CPU tensor is staged."""
+    if getattr(tq, "fp8_maxval", None) is None:
+        raise ValueError("tensor_quantizer.fp8_maxval not present or not initialized!")
+    M = _fp8._mantissa_bits(_fp8.NUM_MANTISSA_BITS)
+    dtype = tensor.dtype
+    t, staged = _fp8._device_fp32(tensor, "tensor")
+    C = tq.fp8_maxval.numel()
+    if C == 1:
+        outer, K = 1, t.numel()
+    else:
+        outer, C, K = per_channel_view(t.shape, tq.channel_axis or 0)
+        if C != tq.fp8_maxval.numel():
+            raise ValueError("tensor has %d channels, fp8_maxval has %d" % (C, tq.fp8_maxval.numel()))
+    out = torch.empty_like(t)
+    if t.numel():
+        table = tq.fp8_table(t.device, M)
+        with torch.cuda.device(t.device):
+            _native.call("aimet_fp8_qdq", t.data_ptr(), out.data_ptr(), outer, C, K, table.data_ptr(), M, _stream(t))
+    out = out.to(dtype)
+    return out.cpu() if staged else out
 
 
 class QuantizeDequantize(torch.autograd.Function):

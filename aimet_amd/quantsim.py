@@ -128,13 +128,14 @@ class QuantizationSimModel:
                  quantizable_types=DEFAULT_QUANTIZABLE_TYPES):
         if isinstance(quant_scheme, str):
             quant_scheme = _SCHEME_NAMES[quant_scheme]
-        if default_data_type != QuantizationDataType.int:
+        if default_data_type != QuantizationDataType.int and quant_scheme in _RANGE_LEARNING:
             raise NotImplementedError("float (fp8/fp16) quantization is outside the MI355X integer QDQ core")
         self.model = model if in_place else copy.deepcopy(model)
         self._quant_scheme = quant_scheme
         self._rounding_mode = rounding_mode
         self._default_output_bw = default_output_bw
         self._default_param_bw = default_param_bw
+        self._default_data_type = default_data_type
         self._percentile_value = 100
         self._cfg = _load_config(config_file)
         self._excluded_layer_names = []
@@ -148,7 +149,8 @@ class QuantizationSimModel:
                                                get_v1_quant_scheme_for_initialization(quant_scheme),
                                                is_output_quantized=True,
                                                is_symmetric=self._cfg["act_symmetric"],
-                                               num_inputs=n_inputs.get(id(child), 1))
+                                               num_inputs=n_inputs.get(id(child), 1),
+                                               data_type=default_data_type)
                     for pname, pq in w.param_quantizers.items():
                         pq.use_symmetric_encodings = self._cfg["param_symmetric"]
                         if pname == "bias":
@@ -216,7 +218,9 @@ class QuantizationSimModel:
         encodings of one device fed every rank's samples. Every rank must then call
         compute_encodings and run the same number of model forwards. `sharded=False` keeps the
         reference's behaviour (each rank calibrates on its own data alone), e.g. to calibrate on
-        one rank only; `sharded=True` insists on a process group."""
+        one rank only; `sharded=True` insists on a process group. Sharded calibration keeps refusing
+        the quantizers whose statistics it cannot exchange; the float (FP8) quantizers, whose
+        statistic is the running fp8_maxval, are among them."""
         from aimet_amd import distributed as D
         world = D._world(process_group)
         if sharded is None:
@@ -305,7 +309,8 @@ class QuantizationSimModel:
             scheme = QuantScheme.post_training_tf_enhanced
         per_channel = self._cfg["per_channel_quantization"]
         return {"quant_scheme": scheme.name, "param_bitwidth": self._default_param_bw,
-                "activation_bitwidth": self._default_output_bw, "dtype": "int",
+                "activation_bitwidth": self._default_output_bw,
+                "dtype": self.__dict__.get("_default_data_type", QuantizationDataType.int).name,
                 "is_symmetric": self._cfg["param_symmetric"] if self._cfg["param_symmetric_given"] else per_channel,
                 "per_channel_quantization": per_channel}
 
@@ -469,6 +474,7 @@ def _reset_many(wrappers):
             elif not q._is_encoding_frozen:
                 ops.append(q._op())
                 q._encoding = None
+                q.fp8_maxval = None
     if ops:
         AimetTensorQuantizer.resetEncodingStatsMany(ops)
 

@@ -699,6 +699,46 @@ int aimet_seqmse_recon_sums(const float* xw, const float* xqwq, int64_t outer, i
                             int64_t count, int loss_kind, float* err, float* sig, void* workspace,
                             int64_t workspace_bytes, void* stream);
 
+/* ---- FP8 fake-quantization (aimet_torch/fp_quantization.py) -------------------------------------
+ * mantissa_bits M in 1..6, E = 7 - M exponent bits, subnormals, no NaN / Inf code, the bias set by
+ * maxval. F = (2 - 2^-M) * 2^(2^E - 1), alpha = float32(double(maxval) / F); per element
+ *   xc = clamp(x, -maxval, maxval), q = xc / alpha (IEEE fp32), g = q rounded to M fraction bits at
+ *   exponent max(floor(log2|q|), 1) (ties to even, |g| <= F), out = float32(g * alpha).
+ * +-0 keeps its sign, NaN stays NaN, +-Inf clamps. maxval <= 0 or not finite, or alpha == 0:
+ * out = xc. */
+#define AIMET_FP8_NUM_CANDIDATES 111
+
+/* table_dev [C][2] = {maxval, alpha} from maxval_dev[C], one launch, nothing read back. */
+int aimet_fp8_scale_table(const float* maxval_dev, int64_t C, int mantissa_bits, float* table_dev, void* stream);
+
+/* fp32 QDQ of in [outer][C][K] with channel c's pair of table_dev; C == 1 is per tensor. */
+int aimet_fp8_qdq(const float* in, float* out, int64_t outer, int64_t C, int64_t K, const float* table_dev,
+                  int mantissa_bits, void* stream);
+
+/* Bytes of workspace aimet_fp8_absmax and aimet_fp8_mse_search need for these sizes. */
+int aimet_fp8_search_workspace(int64_t outer, int64_t C, int64_t K, int64_t* bytes);
+
+/* absmax_dev[c] = max |in[o][c][k]| (NaN ignored): init_minmax, and the search's input. */
+int aimet_fp8_absmax(const float* in, int64_t outer, int64_t C, int64_t K, float* absmax_dev, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
+/* init_mse: per channel the 111 candidates torch.linspace(0.1 * mx, 1.2 * mx, 111) (CPU float32
+ * bits, built on the device from absmax_dev), the sum of squared errors of the cast at each, and the
+ * first candidate of least error -> best_maxval_dev[C]. Optional outputs (NULL to skip):
+ * losses_dev [C][111], candidates_dev [111][C], best_index_dev [C]. `in` is read once; per-workgroup
+ * partial sums in `workspace` are added in a fixed order by a second pass (no atomics, a grid that
+ * depends on the shape alone): equal inputs give equal bits. exact_divide == 0: q = xc * RN(1/alpha)
+ * inside the search (moves only elements at a rounding tie); != 0: the IEEE divide of the cast. */
+/* Elements a lane of the search holds while the candidates go by: 4, 8 or 16; 0 restores the
+ * measured default. For the study in benchmarks/fp8_quantsim.py and the tests; sums are added in
+ * another order under another value. */
+int aimet_fp8_search_elems(int elems, int* previous);
+
+int aimet_fp8_mse_search(const float* in, int64_t outer, int64_t C, int64_t K, const float* absmax_dev,
+                         int mantissa_bits, int exact_divide, float* best_maxval_dev, float* losses_dev,
+                         float* candidates_dev, int32_t* best_index_dev, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
