@@ -207,6 +207,10 @@ _PROTOTYPES = {
     "aimet_fp8_absmax": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp],
     "aimet_fp8_search_elems": [_int, ctypes.POINTER(_int)],
     "aimet_fp8_mse_search": [_vp, _i64, _i64, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "aimet_gptvq_kmeans": [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp],
+    "aimet_gptvq_block_update": [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp,
+                                 _vp],
+    "aimet_gptvq_update_layout": [_int, ctypes.POINTER(_int)],
 }
 _RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p}
 

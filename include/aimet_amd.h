@@ -739,6 +739,44 @@ int aimet_fp8_mse_search(const float* in, int64_t outer, int64_t C, int64_t K, c
                          float* candidates_dev, int32_t* best_index_dev, void* workspace, int64_t workspace_bytes,
                          void* stream);
 
+/* ---- GPTVQ (aimet_torch/gptvq/) -------------------------------------------------------------------
+ * W2d is the [rows][cols] fp32 weight with leading dimension ld, G = rows / rows_per_block row
+ * groups, D = vector_dim (1..8), K = 2^index_bw centroids (1..1024). All arithmetic is fp32, every
+ * product and sum rounded on its own, divides IEEE; "first minimum" is the smallest index among
+ * equal distances; dist(x, c) = sum over d ascending of (x_d - c_d) * (x_d - c_d). */
+
+/* generate_codebook's Lloyd loop (gptvq/utils.py:72-77) for one column block, `iterations` steps in
+ * one launch. w points at W2d[0][c0]; ncols (a multiple of D) columns belong to this codebook.
+ * Group g owns N = rows_per_block * ncols / D vectors, vector n = r * (ncols / D) + t being
+ * w[(g * rows_per_block + r) * ld + t * D + d]. codebook [G][K][D]: the initial centroids on entry,
+ * the result on return. E-step: first minimum over k of dist. M-step: c_k = (sum of the assigned
+ * vectors) * (1.0f / max(count_k, 1)), an empty cluster becoming zero. The sum runs in a fixed
+ * order (see gptvq.hip) without atomics: equal inputs give equal bits. One workgroup per group,
+ * the group's vectors staged in LDS (in chunks re-read from global memory when they do not fit).
+ * G * rows_per_block * ld, rows_per_block * ncols and G * K * D below 2^31. */
+int aimet_gptvq_kmeans(const float* w, int64_t ld, int64_t G, int64_t rows_per_block, int64_t ncols, int32_t D,
+                       int32_t K, int32_t iterations, float* codebook, void* stream);
+
+/* The inner loop of GPTVQOptimizer.weight_update (gptvq_optimizer.py:140-166) for the steps
+ * i = s0, s0 + D, ... < s1 of the column block [b0, block_end) (at most 128 columns; s0, s1 and the
+ * length multiples of D), in one launch, w updated in place. For every row r, with its group's
+ * codebook [K][D] and hinv the upper Cholesky factor of the inverse Hessian:
+ *   x_d = w[r][b0 + i + d]; k* = first minimum of dist(x, c_k); q = codebook[g][k*];
+ *   e_d = (x_d - q_d) / hinv[b0 + i + d][b0 + i + d]; w[r][b0 + i + d] = q_d;
+ *   w[r][j] -= (e_0 * hinv[b0 + i][j] + e_1 * hinv[b0 + i + 1][j] + ...) for b0 + i + D <= j < block_end;
+ *   err[r][i + d] = e_d; indices[r][i / D] = k*.
+ * err is [rows][block_end - b0], indices [rows][(block_end - b0) / D] (int32); only the entries of
+ * the steps of this call are written. Columns outside [b0, block_end) are not touched. rows * ld
+ * and hinv_ld * block_end below 2^31. */
+int aimet_gptvq_block_update(float* w, int64_t ld, int64_t rows, int64_t rows_per_block, int64_t b0, int64_t s0,
+                             int64_t s1, int64_t block_end, int32_t D, int32_t K, const float* codebook,
+                             const float* hinv, int64_t hinv_ld, float* err, int32_t* indices, void* stream);
+
+/* Lane layout of aimet_gptvq_block_update: 1 a wave per row, 2 a lane per row; 0 restores the
+ * measured default. For the study in benchmarks/gptvq_llama.py and the tests; the results are the
+ * same bits under every layout. */
+int aimet_gptvq_update_layout(int layout, int* previous);
+
 #ifdef __cplusplus
 }
 #endif
