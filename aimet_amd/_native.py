@@ -72,6 +72,20 @@ class QcQuantizeInfoC(ctypes.Structure):
 
 _i64p = ctypes.POINTER(ctypes.c_int64)
 
+
+class DfqWeightC(ctypes.Structure):
+    """aimet_dfq_weight: element (o, i, j) at data[o * out_stride + i * in_stride + j]."""
+    _fields_ = [("data", ctypes.c_void_p), ("cout", ctypes.c_int64), ("cin", ctypes.c_int64), ("k", ctypes.c_int64),
+                ("out_stride", ctypes.c_int64), ("in_stride", ctypes.c_int64)]
+
+
+class DfqBnFoldJobC(ctypes.Structure):
+    """aimet_dfq_bn_fold_job."""
+    _fields_ = [("w", DfqWeightC), ("bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+                ("mean", ctypes.c_void_p), ("var", ctypes.c_void_p), ("eps", ctypes.c_float),
+                ("forward", ctypes.c_int32)]
+
+
 # name -> argtypes (restype is int status unless listed in _RESTYPES)
 _PROTOTYPES = {
     "aimet_last_error": [],
@@ -211,6 +225,12 @@ _PROTOTYPES = {
     "aimet_gptvq_block_update": [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp,
                                  _vp],
     "aimet_gptvq_update_layout": [_int, ctypes.POINTER(_int)],
+    "aimet_dfq_bn_fold": [ctypes.POINTER(DfqBnFoldJobC), _i64, _vp, _vp],
+    "aimet_dfq_cls_pair": [ctypes.POINTER(DfqWeightC), _vp, ctypes.POINTER(DfqWeightC), _vp, _vp],
+    "aimet_dfq_cls_triple": [ctypes.POINTER(DfqWeightC), _vp, ctypes.POINTER(DfqWeightC), _vp,
+                             ctypes.POINTER(DfqWeightC), _vp, _vp, _vp],
+    "aimet_dfq_bias_fold": [_vp, _vp, _vp, _i64, _int, _vp, ctypes.POINTER(DfqWeightC), _vp, _vp],
+    "aimet_dfq_launch_count": [_i64p, _int],
 }
 _RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p}
 

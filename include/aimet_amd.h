@@ -777,6 +777,66 @@ int aimet_gptvq_block_update(float* w, int64_t ld, int64_t rows, int64_t rows_pe
  * same bits under every layout. */
 int aimet_gptvq_update_layout(int layout, int* previous);
 
+/* ---- Data-free quantization (aimet_common/batch_norm_fold.py, cross_layer_equalization.py) ---------
+ * BN fold, cross-layer scaling and high-bias fold, in place on fp32 parameters in device memory. One
+ * workgroup owns one channel, so each step is a single launch; no atomics, every reduction in an
+ * order fixed by the sizes alone (equal inputs give equal bits). Every product, quotient and root is
+ * its own rounded fp32 operation (IEEE divide and sqrt, no contraction, denormals kept).
+ *
+ * A weight is cout x cin x k floats, element (o, i, j) at data[o * out_stride + i * in_stride + j]:
+ * (out_stride, in_stride) is (cin * k, k) for Conv / Linear layouts and (k, cout * k) for
+ * ConvTranspose with groups == 1 (channels on axis 1). Nothing else is accepted. */
+typedef struct aimet_dfq_weight
+{
+    float* data;
+    int64_t cout, cin, k, out_stride, in_stride;
+} aimet_dfq_weight;
+
+/* One fold of aimet_dfq_bn_fold. scale = gamma / sqrt(var + eps).
+ * forward == 0 (conv -> bn, the four vectors cout long): w[o,:,:] *= scale[o],
+ *   b[o] = beta[o] - (mu[o] - b[o]) * scale[o].
+ * forward != 0 (bn -> conv, the vectors cin long, Conv / Linear layout only):
+ *   b[o] = (sum_i w2d[o,i] * beta[i] - sum_i w2d[o,i] * (mu[i] * scale[i])) + b[o] with
+ *   w2d[o,i] = sum_j w[o,i,j] of the weight before scaling, then w[:,i,:] *= scale[i].
+ * A channel whose sqrt(var + eps) is zero is left as it was and the job's status word is set to 1. */
+typedef struct aimet_dfq_bn_fold_job
+{
+    aimet_dfq_weight w;
+    float* bias;
+    const float* gamma;
+    const float* beta;
+    const float* mean;
+    const float* var;
+    float eps;
+    int32_t forward;
+} aimet_dfq_bn_fold_job;
+
+/* `count` independent folds (host table, no two on the same weight) in one launch, grid (job,
+ * output channel). status_dev: `count` int32 in device memory, zeroed by the caller. */
+int aimet_dfq_bn_fold(const aimet_dfq_bn_fold_job* jobs, int64_t count, int32_t* status_dev, void* stream);
+
+/* compute_scaling_params_for_conv + fold_scaling_params_for_conv, C = w0.cout = w1.cin channels:
+ *   r0 = max|w0[c,:,:]|, r1 = max|w1[:,c,:]|, s = r0 / sqrt(r0 * r1); NaN and +inf -> 1, then 0 -> 1;
+ *   w0[c] *= 1/s, bias0[c] *= 1/s (bias0 may be NULL), w1[:,c] *= s; scale_dev[c] = s. */
+int aimet_dfq_cls_pair(const aimet_dfq_weight* w0, float* bias0, const aimet_dfq_weight* w1, float* scale_dev,
+                       void* stream);
+
+/* The depthwise-separable triple (w1: C x 1 x k): p = (r0 * r1) * r2, root = (float) cbrt((double) p),
+ *   s12 = r0 / root, s23 = root / r2 (sanitised as above); w0[c] *= 1/s12, w1[c] = w1[c] * s12 * (1/s23),
+ *   w2[:,c] *= s23, bias0[c] *= 1/s12, bias1[c] *= 1/s23 (either bias may be NULL). */
+int aimet_dfq_cls_triple(const aimet_dfq_weight* w0, float* bias0, const aimet_dfq_weight* w1, float* bias1,
+                         const aimet_dfq_weight* w2, float* s12_dev, float* s23_dev, void* stream);
+
+/* _absorb_bias for one pair, C channels between the layers:
+ *   absorb[c] = relu_between ? max(0, beta[c]/scale[c] - 3 * |gamma[c]/scale[c]|) : beta[c]/scale[c];
+ *   bias1[c] -= absorb[c]; w2.cin == C: bias2[o] += sum_c (sum_j w2[o,c,j]) * absorb[c];
+ *   w2.cin == 1 (depthwise, w2.cout == C): bias2[o] += (sum_j w2[o,0,j]) * absorb[o]. */
+int aimet_dfq_bias_fold(const float* gamma, const float* beta, const float* scale, int64_t C, int relu_between,
+                        float* bias1, const aimet_dfq_weight* w2, float* bias2, void* stream);
+
+/* Kernel launches the four entry points above have issued in this process; reset != 0 zeroes it. */
+int aimet_dfq_launch_count(int64_t* count, int reset);
+
 #ifdef __cplusplus
 }
 #endif
