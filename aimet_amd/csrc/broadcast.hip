@@ -13,7 +13,9 @@
 // 2-3 dims. The kernel then does one 32-bit multiply-shift division per merged dim per 4
 // elements (16-B vectors whenever the innermost run allows), and gathers the per-element
 // encoding from the four float arrays (L1/L2-resident: E << N).
+// The fp16 round trip is an op (Fp16RoundTrip) on the kernels and launch policy of stream_map.hpp.
 #include "common.hpp"
+#include "stream_map.hpp"
 
 #include <vector>
 
@@ -23,7 +25,6 @@ namespace
 {
 
 constexpr int kMaxMerged = 8;
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // A collapsed row-major view: dim d has `size`, tensor stride `tstride` (contiguous) and
 // encoding stride `estride` (0 along broadcast dims).
@@ -341,35 +342,28 @@ __device__ __forceinline__ float fp16_rt(float x)
     return (float) (_Float16) x;
 }
 
-// one float4 per lane, one LANES-lane tile per workgroup (the tensor_vec_kernel form: 6.4 TB/s at
-// 256 lanes where a 2048-workgroup grid-stride loop reached 5.2). 64 lanes: +2.5 % in the sweep and
-// +2.7 % in benchmarks/kernel_roofline.py, short of three times that row's run-to-run spread, so
-// 256 lanes stays (profiles/r07/qdq_tile_sweep.txt)
+// 6.4 TB/s at 256 lanes where a 2048-workgroup grid-stride loop reached 5.2. 64 lanes: +2.5 % in
+// the sweep and +2.7 % in benchmarks/kernel_roofline.py, short of three times that row's
+// run-to-run spread, so 256 lanes stays (profiles/r07/qdq_tile_sweep.txt)
 constexpr int kFp16Lanes = 256;
-template <int LANES>
-__global__ __launch_bounds__(LANES) void fp16_vec_kernel(const f4* __restrict__ in, f4* __restrict__ out,
-                                                         int64_t nvec)
+struct Fp16RoundTrip
 {
-    const int64_t i = (int64_t) blockIdx.x * LANES + threadIdx.x;
-    if (i >= nvec)
-        return;
-    f4 x = __builtin_nontemporal_load(in + i);
-    f4 r {fp16_rt(x.x), fp16_rt(x.y), fp16_rt(x.z), fp16_rt(x.w)};
-    __builtin_nontemporal_store(r, out + i);
-}
-
-__global__ __launch_bounds__(kBlock) void fp16_scalar_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                             int64_t begin, int64_t n)
-{
-    const int64_t stride = (int64_t) gridDim.x * kBlock;
-    for (int64_t i = begin + (int64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+    using index_t      = int64_t;
+    using tail_index_t = int64_t;
+    static constexpr int width = 4;
+    const float* __restrict__ in;
+    float* __restrict__ out;
+    __device__ __forceinline__ void vec(int64_t i) const
+    {
+        f4 x = load_stream(reinterpret_cast<const f4*>(in) + i);
+        f4 r {fp16_rt(x.x), fp16_rt(x.y), fp16_rt(x.z), fp16_rt(x.w)};
+        store_stream(r, reinterpret_cast<f4*>(out) + i);
+    }
+    __device__ __forceinline__ void scalar(int64_t i) const
+    {
         out[i] = fp16_rt(in[i]);
-}
-
-inline bool aligned16(const void* a, const void* b)
-{
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
-}
+    }
+};
 
 }   // namespace
 
@@ -437,28 +431,7 @@ void launch_permute(const float* in, float* out, int64_t n, int64_t nd, const in
 
 void launch_qdq_fp16(const float* in, float* out, int64_t n, hipStream_t s)
 {
-    if (n == 0)
-        return;
-    int64_t done = 0;
-    if (aligned16(in, out))
-    {
-        int64_t nvec = n / 4;
-        if (nvec)
-        {
-            with_lanes(tile_lanes(kFp16Lanes), [&](auto L) {
-                constexpr int LANES = decltype(L)::value;
-                fp16_vec_kernel<LANES><<<tile_grid(nvec, LANES), LANES, 0, s>>>(reinterpret_cast<const f4*>(in),
-                                                                              reinterpret_cast<f4*>(out), nvec);
-            });
-            AIMET_LAUNCH_CHECK();
-        }
-        done = nvec * 4;
-    }
-    if (done < n)
-    {
-        fp16_scalar_kernel<<<stream_blocks(n - done, kBlock), kBlock, 0, s>>>(in, out, done, n);
-        AIMET_LAUNCH_CHECK();
-    }
+    launch_stream<kFp16Lanes>(Fp16RoundTrip {in, out}, n, aligned16(in, out), s);
 }
 
 }   // namespace aimet_amd

@@ -19,9 +19,9 @@
 // MI355X design:
 //   * scale_table: {maxval, alpha} per channel from maxvals in HBM, one small launch, nothing read
 //     back: a forward stays capturable in a HIP graph.
-//   * qdq: HBM-bound, 8 B/element, the shape of qdq.hip's integer kernels: one 16-B vector per
-//     lane, one tile per single-wave workgroup, non-temporal loads / stores, the channel's pair
-//     fetched once per vector (K % 4 == 0), scalar tail and unaligned fallback.
+//   * qdq: HBM-bound, 8 B/element, two ops (Fp8Tensor, Fp8Channel) on the streaming skeleton of
+//     stream_map.hpp at one wave per workgroup; the channel's pair is fetched once per vector
+//     (K % 4 == 0).
 //   * search: ALU-bound (111 casts per element read). A single-wave workgroup owns a run of
 //     1024-element tiles of one [outer][C] row; a lane keeps 16 elements of the tile in registers
 //     while the 111 candidates go by, so four partial sums are live at a time (not 111) and the
@@ -31,6 +31,7 @@
 //     alone, results repeat bit for bit. The candidate maxima are torch.linspace's float32 values,
 //     built on the device from max|x|.
 #include "common.hpp"
+#include "stream_map.hpp"
 
 #include <atomic>
 #include <cmath>
@@ -41,9 +42,7 @@ namespace aimet_amd
 namespace
 {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int kFp8Lanes   = 64;     // qdq vector kernels: one wave per workgroup (qdq.hip's sweep)
+constexpr int kFp8Lanes   = 64;     // family default of the qdq ops (stream_map.hpp: launch_stream)
 constexpr int kCand       = 111;    // init_mse: linspace(0.1 * mx, 1.2 * mx, 111)
 constexpr int kSearchElems = 16;    // elements a lane holds while the candidates go by (4, 8 or 16)
 constexpr int kSearchTile = 64 * 16;    // the unit of the grid's plan, whatever a lane holds
@@ -127,62 +126,53 @@ __device__ __forceinline__ f4 fp8_cast4(f4 v, float mv, float alpha, const Fp8Fo
     return r;
 }
 
-template <int LANES>
-__global__ __launch_bounds__(LANES) void fp8_tensor_vec_kernel(const f4* __restrict__ in, f4* __restrict__ out,
-                                                               int64_t nvec, const float* __restrict__ table,
-                                                               Fp8Format f)
+// per-tensor (C == 1): table = {maxval, alpha}
+struct Fp8Tensor
 {
-    const int64_t i = (int64_t) blockIdx.x * LANES + threadIdx.x;
-    if (i >= nvec)
-        return;
-    const f4 v = __builtin_nontemporal_load(in + i);
-    __builtin_nontemporal_store(fp8_cast4(v, table[0], table[1], f), out + i);
-}
-
-__global__ __launch_bounds__(kBlock) void fp8_tensor_scalar_kernel(const float* __restrict__ in,
-                                                                   float* __restrict__ out, int64_t begin, int64_t n,
-                                                                   const float* __restrict__ table, Fp8Format f)
-{
-    const float mv = table[0], alpha = table[1];
-    const int64_t stride = (int64_t) gridDim.x * kBlock;
-    for (int64_t i = begin + (int64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
-        out[i] = fp8_cast(in[i], mv, alpha, f);
-}
-
-// K % 4 == 0: a 16-B vector never straddles two channels
-template <int LANES>
-__global__ __launch_bounds__(LANES) void fp8_channel_vec_kernel(const f4* __restrict__ in, f4* __restrict__ out,
-                                                                uint32_t nvec, FastDiv divK, FastDiv divC,
-                                                                const float* __restrict__ table, Fp8Format f)
-{
-    const uint32_t i = blockIdx.x * LANES + threadIdx.x;
-    if (i >= nvec)
-        return;
-    const f4 v         = __builtin_nontemporal_load(in + i);
-    const uint32_t row = divK.div(i * 4);
-    const uint32_t c   = row - divC.div(row) * divC.d;
-    const float2 p     = reinterpret_cast<const float2*>(table)[c];
-    __builtin_nontemporal_store(fp8_cast4(v, p.x, p.y, f), out + i);
-}
-
-// any K and alignment, and tensors of >= 2^31 elements
-__global__ __launch_bounds__(kBlock) void fp8_channel_scalar_kernel(const float* __restrict__ in,
-                                                                    float* __restrict__ out, int64_t n, int64_t C,
-                                                                    int64_t K, const float* __restrict__ table,
-                                                                    Fp8Format f)
-{
-    const int64_t stride = (int64_t) gridDim.x * kBlock;
-    for (int64_t i = (int64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+    using index_t      = int64_t;
+    using tail_index_t = int64_t;
+    static constexpr int width = 4;
+    const float* __restrict__ in;
+    float* __restrict__ out;
+    const float* __restrict__ table;
+    Fp8Format f;
+    __device__ __forceinline__ void vec(int64_t i) const
     {
+        const f4 v = load_stream(reinterpret_cast<const f4*>(in) + i);
+        store_stream(fp8_cast4(v, table[0], table[1], f), reinterpret_cast<f4*>(out) + i);
+    }
+    __device__ __forceinline__ void scalar(int64_t i) const
+    {
+        out[i] = fp8_cast(in[i], table[0], table[1], f);
+    }
+};
+
+// vector form: K % 4 == 0 (a 16-B vector never straddles two channels), n < 2^31; scalar form:
+// int64, any K and alignment
+struct Fp8Channel
+{
+    using index_t      = uint32_t;
+    using tail_index_t = int64_t;
+    static constexpr int width = 4;
+    const float* __restrict__ in;
+    float* __restrict__ out;
+    ChannelMap map;
+    int64_t C, K;
+    const float* __restrict__ table;
+    Fp8Format f;
+    __device__ __forceinline__ void vec(uint32_t i) const
+    {
+        const f4 v     = load_stream(reinterpret_cast<const f4*>(in) + i);
+        const float2 p = reinterpret_cast<const float2*>(table)[map.channel(i * 4)];
+        store_stream(fp8_cast4(v, p.x, p.y, f), reinterpret_cast<f4*>(out) + i);
+    }
+    __device__ __forceinline__ void scalar(int64_t i) const
+    {
+        independent_of(out, in, table);
         const int64_t c = (i / K) % C;
         out[i]          = fp8_cast(in[i], table[2 * c], table[2 * c + 1], f);
     }
-}
-
-inline bool aligned16(const void* a, const void* b)
-{
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
-}
+};
 
 // ---------------------------------------------------------------------------------------------
 // range search
@@ -501,38 +491,10 @@ int aimet_fp8_qdq(const float* in, float* out, int64_t outer, int64_t C, int64_t
         require_device_ptr(table_dev, "table");
         hipStream_t s = as_stream(stream);
         if (C == 1)
-        {
-            const int64_t nvec = aligned16(in, out) ? n / 4 : 0;
-            if (nvec > 0)
-            {
-                with_lanes(tile_lanes(kFp8Lanes), [&](auto L) {
-                    constexpr int LANES = decltype(L)::value;
-                    fp8_tensor_vec_kernel<LANES><<<tile_grid(nvec, LANES), LANES, 0, s>>>(
-                        reinterpret_cast<const f4*>(in), reinterpret_cast<f4*>(out), nvec, table_dev, f);
-                });
-                AIMET_LAUNCH_CHECK();
-            }
-            if (nvec * 4 < n)
-            {
-                fp8_tensor_scalar_kernel<<<stream_blocks(n - nvec * 4, kBlock), kBlock, 0, s>>>(in, out, nvec * 4, n,
-                                                                                              table_dev, f);
-                AIMET_LAUNCH_CHECK();
-            }
-            return;
-        }
-        if (n < (int64_t(1) << 31) && K % 4 == 0 && aligned16(in, out))
-        {
-            const uint32_t nvec = (uint32_t) (n / 4);
-            with_lanes(tile_lanes(kFp8Lanes), [&](auto L) {
-                constexpr int LANES = decltype(L)::value;
-                fp8_channel_vec_kernel<LANES><<<tile_grid(nvec, LANES), LANES, 0, s>>>(
-                    reinterpret_cast<const f4*>(in), reinterpret_cast<f4*>(out), nvec, FastDiv((uint32_t) K),
-                    FastDiv((uint32_t) C), table_dev, f);
-            });
-        }
+            launch_stream<kFp8Lanes>(Fp8Tensor {in, out, table_dev, f}, n, aligned16(in, out), s);
         else
-            fp8_channel_scalar_kernel<<<stream_blocks(n, kBlock), kBlock, 0, s>>>(in, out, n, C, K, table_dev, f);
-        AIMET_LAUNCH_CHECK();
+            launch_stream<kFp8Lanes>(Fp8Channel {in, out, ChannelMap(C, K), C, K, table_dev, f}, n,
+                                     n < (int64_t(1) << 31) && K % 4 == 0 && aligned16(in, out), s);
     });
 }
 

@@ -1,27 +1,31 @@
-// qdq.hip -- quantize-dequantize, quantize-only and STE-backward kernels for gfx950.
+// qdq.hip -- quantize-dequantize, quantize-only and STE-backward ops for gfx950, and the batched
+// per-channel plan kernel.
 //
 // Reference: trim_functions.cu:46-92 (one element per thread, 512-thread blocks, fast-math
 // division, per-element global loads of the per-channel table, legacy default stream).
 // The per-element IEEE division stays (tools/studies/qdq_variants.hip: the reciprocal fast path of
 // common.hpp measures 4% slower here -- this kernel is HBM-bound, the fast path's extra VGPRs and
 // branch cost more than the division; it pays off in the 16-bit and histogram kernels).
-// MI355X design: HBM-bound streaming (8 B/elem fwd, 12 B/elem STE) -> one 16-B vector per lane,
-// one tile per single-wave (64-lane) workgroup (STE: 256), non-temporal loads/stores (streamed once, kept out
-// of L2/MALL), scalar encoding parameters in SGPRs, per-channel parameters fetched once per 16-B
-// vector (K % 4 == 0) from a device-resident table built once per encoding.
-// The tile shape is a template parameter (64 / 128 / 256 lanes), chosen from a sweep through the
-// library itself, back-to-back launches from a HIP graph over fresh memory
-// (tools/studies/qdq_tile_sweep.hip, profiles/r07/qdq_tile_sweep.txt), 64 / 128 / 256 lanes:
+// MI355X design: HBM-bound streaming (8 B/elem fwd, 12 B/elem STE). The ops below (TensorQdq,
+// ChannelQdq, ChannelQdq64, SteTensor, SteChannel) run on stream_map.hpp's two kernels, and its
+// launch_stream holds the launch policy: one 16-B vector per lane, one tile per single-wave
+// (64-lane) workgroup (STE: 256), non-temporal loads/stores. Scalar encoding parameters are kernel
+// arguments (SGPRs), per-channel parameters are fetched once per 16-B vector (K % 4 == 0) from a
+// device-resident table built once per encoding.
+// The family defaults come from a sweep through the library itself, back-to-back launches from a
+// HIP graph over fresh memory (tools/studies/qdq_tile_sweep.hip, profiles/r07/qdq_tile_sweep.txt),
+// 64 / 128 / 256 lanes:
 //   per-tensor, 6.4 M elements      5.28 / 5.04 / 5.12 TB/s     205.5 M      6.77 / 6.60 / 6.56 TB/s
 //   the flagship step's 53 launches of its six sizes, byte-weighted: 6.63 / 6.42 / 6.38 TB/s
 //   per-channel 256x64x12544        6.75 / 6.47 / 6.45 TB/s     STE 205.5 M  6.59 / 6.49 / 6.42 TB/s
 //   batched plan, 54 ResNet-50 weights (25.5 M elements): 6.11 / 5.64 / 5.74 TB/s
 // One wave per workgroup wins at every size and 128 lanes is within 1 % of 256, so there is no
-// size threshold; the flagship step went from 3.594 to 3.456 ms of tensor_vec_kernel time
+// size threshold; the flagship step went from 3.594 to 3.456 ms of per-tensor QDQ kernel time
 // (rocprofv3), 796.0 -> 829.0 Gelem/s. Adopted where the gain cleared three times the parent's
 // run-to-run spread: per-tensor and batched (bench.py), per-channel (benchmarks/kernel_roofline.py:
 // 6.46 -> 6.74 TB/s). The STE kernels' +3.4 % there fell just short, so they stay at 256 lanes.
 #include "common.hpp"
+#include "stream_map.hpp"
 
 #include <atomic>
 #include <cmath>
@@ -50,151 +54,107 @@ __device__ __forceinline__ float apply(float x, const QdqParams& p, float shift,
 }
 
 // ---------------------------------------------------------------------------------------
-// Per-tensor: parameters are kernel arguments (SGPRs). One 16-B vector per lane, one tile per
-// workgroup, non-temporal (streaming) loads and stores: 6.80 TB/s for a 2 GiB in+out stream at
+// Per-tensor: parameters are kernel arguments (SGPRs): 6.80 TB/s for a 2 GiB in+out stream at
 // 64 lanes (6.59 at 256; a grid-strided 4-vector loop with default cache policy reached 5.6:
 // tools/studies/qdq_variants.hip, profiles/r01/qdq_variants.txt).
 // ---------------------------------------------------------------------------------------
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f4 load_stream(const f4* p)
-{
-    return __builtin_nontemporal_load(p);
-}
-__device__ __forceinline__ void store_stream(f4 v, f4* p)
-{
-    __builtin_nontemporal_store(v, p);
-}
-
-// Tile shapes (common.hpp: tile_lanes / with_lanes / tile_grid), one 16-B vector per lane
-constexpr int kTensorLanes  = 64;    // tensor_vec_kernel
-constexpr int kChannelLanes = 64;    // channel_vec_kernel
+// Family defaults of the tile shape (stream_map.hpp: launch_stream), one 16-B vector per lane
+constexpr int kTensorLanes  = 64;    // TensorQdq
+constexpr int kChannelLanes = 64;    // ChannelQdq
 constexpr int kBatchLanes   = 64;    // channel_batch_kernel (fixed per plan at its creation)
-constexpr int kSteLanes     = 256;   // ste_*_vec_kernel (64: +3.4 % in kernel_roofline.py, short of the margin)
+constexpr int kSteLanes     = 256;   // SteTensor / SteChannel (64: +3.4 % in kernel_roofline.py, short of the margin)
 
 std::atomic<int> g_tile_lanes {0};   // aimet_qdq_tile_lanes; 0: the defaults above
 
-template <int LANES, Op OP, bool STOCHASTIC>
-__global__ __launch_bounds__(LANES) void tensor_vec_kernel(const f4* __restrict__ in, f4* __restrict__ out,
-                                                           int64_t nvec, QdqParams p, float shift, uint64_t seed)
-{
-    const int64_t i = (int64_t) blockIdx.x * LANES + threadIdx.x;
-    if (i >= nvec)
-        return;
-    f4 v = load_stream(in + i);
-    uint64_t e = (uint64_t) i * 4;
-    f4 r;
-    r.x = apply<OP, STOCHASTIC>(v.x, p, shift, seed, e + 0);
-    r.y = apply<OP, STOCHASTIC>(v.y, p, shift, seed, e + 1);
-    r.z = apply<OP, STOCHASTIC>(v.z, p, shift, seed, e + 2);
-    r.w = apply<OP, STOCHASTIC>(v.w, p, shift, seed, e + 3);
-    store_stream(r, out + i);
-}
-
 template <Op OP, bool STOCHASTIC>
-__global__ __launch_bounds__(kBlock) void tensor_scalar_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                               int64_t begin, int64_t n, QdqParams p, float shift,
-                                                               uint64_t seed)
+struct TensorQdq
 {
-    const int64_t stride = (int64_t) gridDim.x * kBlock;
-    for (int64_t i = begin + (int64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+    using index_t      = int64_t;
+    using tail_index_t = int64_t;
+    static constexpr int width = 4;
+    const float* __restrict__ in;
+    float* __restrict__ out;
+    QdqParams p;
+    float shift;
+    uint64_t seed;
+    __device__ __forceinline__ void vec(int64_t i) const
+    {
+        f4 v = load_stream(reinterpret_cast<const f4*>(in) + i);
+        uint64_t e = (uint64_t) i * 4;
+        f4 r;
+        r.x = apply<OP, STOCHASTIC>(v.x, p, shift, seed, e + 0);
+        r.y = apply<OP, STOCHASTIC>(v.y, p, shift, seed, e + 1);
+        r.z = apply<OP, STOCHASTIC>(v.z, p, shift, seed, e + 2);
+        r.w = apply<OP, STOCHASTIC>(v.w, p, shift, seed, e + 3);
+        store_stream(r, reinterpret_cast<f4*>(out) + i);
+    }
+    __device__ __forceinline__ void scalar(int64_t i) const
+    {
         out[i] = apply<OP, STOCHASTIC>(in[i], p, shift, seed, (uint64_t) i);
-}
+    }
+};
 
+// the scalar kernel runs from 0 when the pointers are misaligned
 template <Op OP, bool STOCHASTIC>
 void launch_tensor(const float* in, float* out, int64_t n, const QdqParams& p, float shift, uint64_t seed,
                    hipStream_t s)
 {
-    if (n <= 0)
-        return;
-    bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    int64_t nvec = aligned ? n / 4 : 0;
-    if (nvec > 0)
-    {
-        with_lanes(tile_lanes(kTensorLanes), [&](auto L) {
-            constexpr int LANES = decltype(L)::value;
-            tensor_vec_kernel<LANES, OP, STOCHASTIC><<<tile_grid(nvec, LANES), LANES, 0, s>>>(
-                reinterpret_cast<const f4*>(in), reinterpret_cast<f4*>(out), nvec, p, shift, seed);
-        });
-        AIMET_LAUNCH_CHECK();
-    }
-    int64_t done = nvec * 4;
-    if (done < n)
-    {
-        int blocks = stream_blocks(n - done, kBlock);
-        tensor_scalar_kernel<OP, STOCHASTIC><<<blocks, kBlock, 0, s>>>(in, out, done, n, p, shift, seed);
-        AIMET_LAUNCH_CHECK();
-    }
+    launch_stream<kTensorLanes>(TensorQdq<OP, STOCHASTIC> {in, out, p, shift, seed}, n, aligned16(in, out), s);
 }
 
 // ---------------------------------------------------------------------------------------
 // Per-channel: [outer][C][K], table [4][C] = {min, max, delta, offset}.
 // ---------------------------------------------------------------------------------------
-struct ChannelMap
-{
-    FastDiv divK;
-    FastDiv divC;
-    uint32_t C;
-    __device__ __forceinline__ uint32_t channel(uint32_t i) const
-    {
-        uint32_t row = divK.div(i);
-        return row - divC.div(row) * C;
-    }
-};
-
-__device__ __forceinline__ QdqParams load_params(const float* __restrict__ table, uint32_t C, uint32_t c)
-{
-    return QdqParams {table[c], table[C + c], table[2 * C + c], table[3 * C + c]};
-}
-
-// K % 4 == 0: a 16-B vector never straddles two channels.
-template <int LANES, bool STOCHASTIC>
-__global__ __launch_bounds__(LANES) void channel_vec_kernel(const f4* __restrict__ in, f4* __restrict__ out,
-                                                            uint32_t nvec, ChannelMap map,
-                                                            const float* __restrict__ table, uint64_t seed)
-{
-    const uint32_t i = blockIdx.x * LANES + threadIdx.x;
-    if (i >= nvec)
-        return;
-    f4 v        = load_stream(in + i);
-    QdqParams p = load_params(table, map.C, map.channel(i * 4));
-    uint64_t e  = (uint64_t) i * 4;
-    f4 r;
-    r.x = apply<Op::QDQ, STOCHASTIC>(v.x, p, 0.f, seed, e + 0);
-    r.y = apply<Op::QDQ, STOCHASTIC>(v.y, p, 0.f, seed, e + 1);
-    r.z = apply<Op::QDQ, STOCHASTIC>(v.z, p, 0.f, seed, e + 2);
-    r.w = apply<Op::QDQ, STOCHASTIC>(v.w, p, 0.f, seed, e + 3);
-    store_stream(r, out + i);
-}
-
 template <bool STOCHASTIC>
-__global__ __launch_bounds__(kBlock) void channel_scalar_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                                uint32_t n, ChannelMap map,
-                                                                const float* __restrict__ table, uint64_t seed)
+struct ChannelQdq
 {
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+    using index_t      = uint32_t;
+    using tail_index_t = uint32_t;
+    static constexpr int width = 4;
+    const float* __restrict__ in;
+    float* __restrict__ out;
+    ChannelMap map;
+    const float* __restrict__ table;
+    uint64_t seed;
+    // K % 4 == 0: a 16-B vector never straddles two channels.
+    __device__ __forceinline__ void vec(uint32_t i) const
+    {
+        f4 v        = load_stream(reinterpret_cast<const f4*>(in) + i);
+        QdqParams p = load_params(table, map.C, map.channel(i * 4));
+        uint64_t e  = (uint64_t) i * 4;
+        f4 r;
+        r.x = apply<Op::QDQ, STOCHASTIC>(v.x, p, 0.f, seed, e + 0);
+        r.y = apply<Op::QDQ, STOCHASTIC>(v.y, p, 0.f, seed, e + 1);
+        r.z = apply<Op::QDQ, STOCHASTIC>(v.z, p, 0.f, seed, e + 2);
+        r.w = apply<Op::QDQ, STOCHASTIC>(v.w, p, 0.f, seed, e + 3);
+        store_stream(r, reinterpret_cast<f4*>(out) + i);
+    }
+    __device__ __forceinline__ void scalar(uint32_t i) const
     {
         QdqParams p = load_params(table, map.C, map.channel(i));
         out[i]      = apply<Op::QDQ, STOCHASTIC>(in[i], p, 0.f, seed, i);
     }
-}
+};
 
-// 64-bit fallback (tensors of >= 2^31 elements).
+// 64-bit form (tensors of >= 2^31 elements): scalar only.
 template <bool STOCHASTIC>
-__global__ __launch_bounds__(kBlock) void channel_scalar64_kernel(const float* __restrict__ in,
-                                                                  float* __restrict__ out, int64_t n, int64_t C,
-                                                                  int64_t K, const float* __restrict__ table,
-                                                                  uint64_t seed)
+struct ChannelQdq64
 {
-    const int64_t stride = (int64_t) gridDim.x * kBlock;
-    for (int64_t i = (int64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+    using tail_index_t = int64_t;
+    static constexpr int width = 1;
+    const float* __restrict__ in;
+    float* __restrict__ out;
+    int64_t C, K;
+    const float* __restrict__ table;
+    uint64_t seed;
+    __device__ __forceinline__ void scalar(int64_t i) const
     {
+        independent_of(out, in, table);
         uint32_t c  = (uint32_t) ((i / K) % C);
         QdqParams p = load_params(table, (uint32_t) C, c);
         out[i]      = apply<Op::QDQ, STOCHASTIC>(in[i], p, 0.f, seed, (uint64_t) i);
     }
-}
+};
 
 // ---------------------------------------------------------------------------------------
 // STE backward: grad_in = grad * (min <= x <= max)
@@ -204,59 +164,60 @@ __device__ __forceinline__ float ste(float x, float g, float mn, float mx)
     return g * ((mn <= x && x <= mx) ? 1.0f : 0.0f);
 }
 
-template <int LANES>
-__global__ __launch_bounds__(LANES) void ste_tensor_vec_kernel(const f4* __restrict__ x, const f4* __restrict__ g,
-                                                               f4* __restrict__ gi, int64_t nvec, float mn, float mx)
+__device__ __forceinline__ void ste_vec(const float* x, const float* g, float* gi, int64_t i, float mn, float mx)
 {
-    const int64_t i = (int64_t) blockIdx.x * LANES + threadIdx.x;
-    if (i >= nvec)
-        return;
-    f4 a = load_stream(x + i), b = load_stream(g + i), r;
+    f4 a = load_stream(reinterpret_cast<const f4*>(x) + i), b = load_stream(reinterpret_cast<const f4*>(g) + i), r;
     r.x = ste(a.x, b.x, mn, mx);
     r.y = ste(a.y, b.y, mn, mx);
     r.z = ste(a.z, b.z, mn, mx);
     r.w = ste(a.w, b.w, mn, mx);
-    store_stream(r, gi + i);
+    store_stream(r, reinterpret_cast<f4*>(gi) + i);
 }
 
-__global__ __launch_bounds__(kBlock) void ste_scalar_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                            float* __restrict__ gi, int64_t begin, int64_t n,
-                                                            int64_t C, int64_t K, const float* __restrict__ mins,
-                                                            const float* __restrict__ maxs, float smin, float smax,
-                                                            int use_scalars)
+struct SteTensor
 {
-    const int64_t stride = (int64_t) gridDim.x * kBlock;
-    for (int64_t i = begin + (int64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+    using index_t      = int64_t;
+    using tail_index_t = int64_t;
+    static constexpr int width = 4;
+    const float* __restrict__ x;
+    const float* __restrict__ g;
+    float* __restrict__ gi;
+    float mn, mx;
+    __device__ __forceinline__ void vec(int64_t i) const
     {
-        float mn = smin, mx = smax;
-        if (!use_scalars)
-        {
-            int64_t c = (C == 1) ? 0 : (i / K) % C;
-            mn        = mins[c];
-            mx        = maxs[c];
-        }
+        ste_vec(x, g, gi, i, mn, mx);
+    }
+    __device__ __forceinline__ void scalar(int64_t i) const
+    {
         gi[i] = ste(x[i], g[i], mn, mx);
     }
-}
+};
 
-template <int LANES>
-__global__ __launch_bounds__(LANES) void ste_channel_vec_kernel(const f4* __restrict__ x, const f4* __restrict__ g,
-                                                                f4* __restrict__ gi, uint32_t nvec, ChannelMap map,
-                                                                const float* __restrict__ mins,
-                                                                const float* __restrict__ maxs)
+// vector form: 32-bit FastDiv map; scalar form: int64, any K, alignment and size
+struct SteChannel
 {
-    const uint32_t i = blockIdx.x * LANES + threadIdx.x;
-    if (i >= nvec)
-        return;
-    uint32_t c = map.channel(i * 4);
-    float mn = mins[c], mx = maxs[c];
-    f4 a = load_stream(x + i), b = load_stream(g + i), r;
-    r.x = ste(a.x, b.x, mn, mx);
-    r.y = ste(a.y, b.y, mn, mx);
-    r.z = ste(a.z, b.z, mn, mx);
-    r.w = ste(a.w, b.w, mn, mx);
-    store_stream(r, gi + i);
-}
+    using index_t      = uint32_t;
+    using tail_index_t = int64_t;
+    static constexpr int width = 4;
+    const float* __restrict__ x;
+    const float* __restrict__ g;
+    float* __restrict__ gi;
+    ChannelMap map;
+    int64_t C, K;
+    const float* __restrict__ mins;
+    const float* __restrict__ maxs;
+    __device__ __forceinline__ void vec(uint32_t i) const
+    {
+        uint32_t c = map.channel(i * 4);
+        float mn = mins[c], mx = maxs[c];
+        ste_vec(x, g, gi, i, mn, mx);
+    }
+    __device__ __forceinline__ void scalar(int64_t i) const
+    {
+        int64_t c = (C == 1) ? 0 : (i / K) % C;
+        gi[i]     = ste(x[i], g[i], mins[c], maxs[c]);
+    }
+};
 
 // ---------------------------------------------------------------------------------------
 // Batched per-channel QDQ (one launch for many tensors)
@@ -311,12 +272,6 @@ __global__ __launch_bounds__(LANES) void channel_batch_kernel(const BatchDesc* _
         QdqParams p = load_params(d.table, d.map.C, d.map.channel(t));
         d.out[t]    = apply<Op::QDQ, STOCHASTIC>(d.in[t], p, 0.f, seed, ((uint64_t) lo << 40) + t);
     }
-}
-
-inline bool aligned16(const void* a, const void* b, const void* c = nullptr)
-{
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) ==
-           0;
 }
 
 }   // namespace
@@ -378,7 +333,7 @@ int aimet_qdq_channel_plan_create(const aimet_qdq_channel_desc* descs, int64_t c
             b.in         = d.in;
             b.out        = d.out;
             b.table      = d.table;
-            b.map        = ChannelMap {FastDiv((uint32_t) (d.K > 0 ? d.K : 1)), FastDiv((uint32_t) d.C), (uint32_t) d.C};
+            b.map        = ChannelMap(d.C, d.K > 0 ? d.K : 1);
             b.n          = (uint32_t) n;
             b.vec        = (d.K % 4 == 0 && aligned16(d.in, d.out)) ? 1u : 0u;
             b.block0     = (uint32_t) blocks;
@@ -541,40 +496,18 @@ int aimet_qdq_per_channel(const float* in, float* out, int64_t outer, int64_t C,
                       "Unknown rounding mode.");
         bool sto      = round_mode == AIMET_ROUND_STOCHASTIC;
         hipStream_t s = as_stream(stream);
-        if (n >= (int64_t(1) << 31))
-        {
-            int blocks = stream_blocks(n, kBlock);
-            if (sto)
-                channel_scalar64_kernel<true><<<blocks, kBlock, 0, s>>>(in, out, n, C, K, table, seed);
+        auto launch = [&](auto STO) {
+            constexpr bool STOCHASTIC = decltype(STO)::value;
+            if (n >= (int64_t(1) << 31))
+                launch_stream<kChannelLanes>(ChannelQdq64<STOCHASTIC> {in, out, C, K, table, seed}, n, false, s);
             else
-                channel_scalar64_kernel<false><<<blocks, kBlock, 0, s>>>(in, out, n, C, K, table, seed);
-            AIMET_LAUNCH_CHECK();
-            return;
-        }
-        ChannelMap map {FastDiv((uint32_t) K), FastDiv((uint32_t) C), (uint32_t) C};
-        if (K % 4 == 0 && aligned16(in, out))
-        {
-            uint32_t nvec = (uint32_t) (n / 4);
-            with_lanes(tile_lanes(kChannelLanes), [&](auto L) {
-                constexpr int LANES = decltype(L)::value;
-                const unsigned blocks = tile_grid(nvec, LANES);
-                if (sto)
-                    channel_vec_kernel<LANES, true><<<blocks, LANES, 0, s>>>(
-                        reinterpret_cast<const f4*>(in), reinterpret_cast<f4*>(out), nvec, map, table, seed);
-                else
-                    channel_vec_kernel<LANES, false><<<blocks, LANES, 0, s>>>(
-                        reinterpret_cast<const f4*>(in), reinterpret_cast<f4*>(out), nvec, map, table, seed);
-            });
-        }
+                launch_stream<kChannelLanes>(ChannelQdq<STOCHASTIC> {in, out, ChannelMap(C, K), table, seed}, n,
+                                             K % 4 == 0 && aligned16(in, out), s);
+        };
+        if (sto)
+            launch(std::true_type {});
         else
-        {
-            int blocks = stream_blocks(n, kBlock);
-            if (sto)
-                channel_scalar_kernel<true><<<blocks, kBlock, 0, s>>>(in, out, (uint32_t) n, map, table, seed);
-            else
-                channel_scalar_kernel<false><<<blocks, kBlock, 0, s>>>(in, out, (uint32_t) n, map, table, seed);
-        }
-        AIMET_LAUNCH_CHECK();
+            launch(std::false_type {});
     });
 }
 
@@ -588,24 +521,7 @@ int aimet_ste_backward_per_tensor(const float* x, const float* g, float* gi, int
         require_device_ptr(x, "x");
         require_device_ptr(g, "grad");
         require_device_ptr(gi, "grad_in");
-        hipStream_t s = as_stream(stream);
-        int64_t nvec  = aligned16(x, g, gi) ? n / 4 : 0;
-        if (nvec > 0)
-        {
-            with_lanes(tile_lanes(kSteLanes), [&](auto L) {
-                constexpr int LANES = decltype(L)::value;
-                ste_tensor_vec_kernel<LANES><<<tile_grid(nvec, LANES), LANES, 0, s>>>(
-                    reinterpret_cast<const f4*>(x), reinterpret_cast<const f4*>(g), reinterpret_cast<f4*>(gi), nvec,
-                    mn, mx);
-            });
-            AIMET_LAUNCH_CHECK();
-        }
-        if (nvec * 4 < n)
-        {
-            int blocks = stream_blocks(n - nvec * 4, kBlock);
-            ste_scalar_kernel<<<blocks, kBlock, 0, s>>>(x, g, gi, nvec * 4, n, 1, 1, nullptr, nullptr, mn, mx, 1);
-            AIMET_LAUNCH_CHECK();
-        }
+        launch_stream<kSteLanes>(SteTensor {x, g, gi, mn, mx}, n, aligned16(x, g, gi), as_stream(stream));
     });
 }
 
@@ -622,24 +538,8 @@ int aimet_ste_backward(const float* x, const float* g, float* gi, int64_t outer,
         require_device_ptr(gi, "grad_in");
         require_device_ptr(mins, "encoding min");
         require_device_ptr(maxs, "encoding max");
-        hipStream_t s = as_stream(stream);
-        if (n < (int64_t(1) << 31) && K % 4 == 0 && aligned16(x, g, gi))
-        {
-            ChannelMap map {FastDiv((uint32_t) K), FastDiv((uint32_t) C), (uint32_t) C};
-            uint32_t nvec = (uint32_t) (n / 4);
-            with_lanes(tile_lanes(kSteLanes), [&](auto L) {
-                constexpr int LANES = decltype(L)::value;
-                ste_channel_vec_kernel<LANES><<<tile_grid(nvec, LANES), LANES, 0, s>>>(
-                    reinterpret_cast<const f4*>(x), reinterpret_cast<const f4*>(g), reinterpret_cast<f4*>(gi), nvec,
-                    map, mins, maxs);
-            });
-        }
-        else
-        {
-            int blocks = stream_blocks(n, kBlock);
-            ste_scalar_kernel<<<blocks, kBlock, 0, s>>>(x, g, gi, 0, n, C, K, mins, maxs, 0.f, 0.f, 0);
-        }
-        AIMET_LAUNCH_CHECK();
+        launch_stream<kSteLanes>(SteChannel {x, g, gi, ChannelMap(C, K), C, K, mins, maxs}, n,
+                                 n < (int64_t(1) << 31) && K % 4 == 0 && aligned16(x, g, gi), as_stream(stream));
     });
 }
 

@@ -1,4 +1,4 @@
-// qdq16.hip -- fp16 / bf16 I/O variants of the QDQ and STE kernels.
+// qdq16.hip -- fp16 / bf16 I/O variants of the QDQ and STE ops.
 //
 // Reference: a half / bfloat16 tensor is upcast (`tensor.to(torch.float32)`), quantize-dequantized
 // by the fp32 kernel and cast back (`.to(orig dtype)`): v1/tensor_quantizer.py:1116-1139 and
@@ -9,8 +9,10 @@
 // torch's (c10::Half via the hardware cvt, c10::BFloat16 round_to_nearest_even with NaN -> 0x7FC0).
 // The STE backward compares float(x) with the float32 bounds (torch type promotion) and returns
 // grad * mask in the grad dtype.
+// The ops run on the kernels and the launch policy of stream_map.hpp, at a fixed 256 lanes.
 #include "common.hpp"
 #include "io16.hpp"
+#include "stream_map.hpp"
 
 #include <cstdlib>
 
@@ -20,6 +22,8 @@ namespace
 {
 
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int kLanes16 = 256;   // fixed: aimet_qdq_tile_lanes does not apply
 
 // thr = qdq_round_thr(p, rcp) (common.hpp), hoisted by the callers out of their element loops
 template <bool STOCHASTIC>
@@ -33,69 +37,53 @@ __device__ __forceinline__ float qdq(float x, const QdqParams& p, uint64_t seed,
     return dequantize(q, p);
 }
 
-struct ChannelMap16
-{
-    FastDiv divK, divC;
-    uint32_t C;
-    __device__ __forceinline__ uint32_t channel(uint32_t i) const
-    {
-        uint32_t row = divK.div(i);
-        return row - divC.div(row) * C;
-    }
-};
-
-__device__ __forceinline__ QdqParams table_params(const float* __restrict__ t, uint32_t C, uint32_t c)
-{
-    return QdqParams {t[c], t[C + c], t[2 * C + c], t[3 * C + c]};
-}
-
-// per-tensor (CH = false, params in SGPRs) / per-channel (CH = true, K % 8 == 0): one 8-element
-// 16-B vector per lane, one tile per workgroup, streaming loads/stores
+// per-tensor (CH = false, params in SGPRs) / per-channel (CH = true; vector form: K % 8 == 0 and
+// n < 2^32, the 32-bit map; scalar form: int64, any K)
 template <int IO, bool CH, bool STOCHASTIC>
-__global__ __launch_bounds__(kBlock) void qdq16_vec_kernel(const u16x8* __restrict__ in, u16x8* __restrict__ out,
-                                                           int64_t nvec, QdqParams p, ChannelMap16 map,
-                                                           const float* __restrict__ table, uint64_t seed)
+struct Qdq16
 {
-    const int64_t i = (int64_t) blockIdx.x * kBlock + threadIdx.x;
-    if (i >= nvec)
-        return;
-    if constexpr (CH)
-        p = table_params(table, map.C, map.channel((uint32_t) (i * 8)));
-    u16x8 v = __builtin_nontemporal_load(in + i), r;
-    const uint64_t e = (uint64_t) i * 8;
-    const float rcp  = 1.0f / p.delta;
-    const float thr  = qdq_round_thr(p, rcp);
-    if (__builtin_isfinite(p.delta) && __builtin_isfinite(p.offset))
+    using index_t      = int64_t;
+    using tail_index_t = int64_t;
+    static constexpr int width = 8;
+    const unsigned short* __restrict__ in;
+    unsigned short* __restrict__ out;
+    QdqParams params;
+    ChannelMap map;
+    int64_t C, K;
+    const float* __restrict__ table;
+    uint64_t seed;
+    __device__ __forceinline__ void vec(int64_t i) const
     {
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            r[k] = from_f32<IO, false>(qdq<STOCHASTIC>(to_f32<IO>(v[k]), p, seed, e + k, rcp, thr));
-    }
-    else
-    {
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            r[k] = from_f32<IO>(qdq<STOCHASTIC>(to_f32<IO>(v[k]), p, seed, e + k, rcp, thr));
-    }
-    __builtin_nontemporal_store(r, out + i);
-}
-
-template <int IO, bool CH, bool STOCHASTIC>
-__global__ __launch_bounds__(kBlock) void qdq16_scalar_kernel(const unsigned short* __restrict__ in,
-                                                              unsigned short* __restrict__ out, int64_t begin,
-                                                              int64_t n, QdqParams p, int64_t C, int64_t K,
-                                                              const float* __restrict__ table, uint64_t seed)
-{
-    const int64_t stride = (int64_t) gridDim.x * kBlock;
-    for (int64_t i = begin + (int64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
-    {
-        QdqParams q = p;
+        QdqParams p = params;
         if constexpr (CH)
-            q = table_params(table, (uint32_t) C, (uint32_t) ((i / K) % C));
+            p = load_params(table, map.C, map.channel((uint32_t) (i * 8)));
+        u16x8 v = load_stream(reinterpret_cast<const u16x8*>(in) + i), r;
+        const uint64_t e = (uint64_t) i * 8;
+        const float rcp  = 1.0f / p.delta;
+        const float thr  = qdq_round_thr(p, rcp);
+        if (__builtin_isfinite(p.delta) && __builtin_isfinite(p.offset))
+        {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                r[k] = from_f32<IO, false>(qdq<STOCHASTIC>(to_f32<IO>(v[k]), p, seed, e + k, rcp, thr));
+        }
+        else
+        {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                r[k] = from_f32<IO>(qdq<STOCHASTIC>(to_f32<IO>(v[k]), p, seed, e + k, rcp, thr));
+        }
+        store_stream(r, reinterpret_cast<u16x8*>(out) + i);
+    }
+    __device__ __forceinline__ void scalar(int64_t i) const
+    {
+        QdqParams q = params;
+        if constexpr (CH)
+            q = load_params(table, (uint32_t) C, (uint32_t) ((i / K) % C));
         const float rcp = 1.0f / q.delta;
         out[i] = from_f32<IO>(qdq<STOCHASTIC>(to_f32<IO>(in[i]), q, seed, (uint64_t) i, rcp, qdq_round_thr(q, rcp)));
     }
-}
+};
 
 template <int IO>
 __device__ __forceinline__ unsigned short ste16(unsigned short x, unsigned short g, float mn, float mx)
@@ -105,39 +93,36 @@ __device__ __forceinline__ unsigned short ste16(unsigned short x, unsigned short
 }
 
 template <int IO, bool CH>
-__global__ __launch_bounds__(kBlock) void ste16_vec_kernel(const u16x8* __restrict__ x, const u16x8* __restrict__ g,
-                                                           u16x8* __restrict__ gi, int64_t nvec, float smin,
-                                                           float smax, ChannelMap16 map,
-                                                           const float* __restrict__ mins,
-                                                           const float* __restrict__ maxs)
+struct Ste16
 {
-    const int64_t i = (int64_t) blockIdx.x * kBlock + threadIdx.x;
-    if (i >= nvec)
-        return;
-    float mn = smin, mx = smax;
-    if constexpr (CH)
+    using index_t      = int64_t;
+    using tail_index_t = int64_t;
+    static constexpr int width = 8;
+    const unsigned short* __restrict__ x;
+    const unsigned short* __restrict__ g;
+    unsigned short* __restrict__ gi;
+    float smin, smax;
+    ChannelMap map;
+    int64_t C, K;
+    const float* __restrict__ mins;
+    const float* __restrict__ maxs;
+    __device__ __forceinline__ void vec(int64_t i) const
     {
-        const uint32_t c = map.channel((uint32_t) (i * 8));
-        mn               = mins[c];
-        mx               = maxs[c];
-    }
-    u16x8 a = __builtin_nontemporal_load(x + i), b = __builtin_nontemporal_load(g + i), r;
+        float mn = smin, mx = smax;
+        if constexpr (CH)
+        {
+            const uint32_t c = map.channel((uint32_t) (i * 8));
+            mn               = mins[c];
+            mx               = maxs[c];
+        }
+        u16x8 a = load_stream(reinterpret_cast<const u16x8*>(x) + i),
+              b = load_stream(reinterpret_cast<const u16x8*>(g) + i), r;
 #pragma unroll
-    for (int k = 0; k < 8; ++k)
-        r[k] = ste16<IO>(a[k], b[k], mn, mx);
-    __builtin_nontemporal_store(r, gi + i);
-}
-
-template <int IO, bool CH>
-__global__ __launch_bounds__(kBlock) void ste16_scalar_kernel(const unsigned short* __restrict__ x,
-                                                              const unsigned short* __restrict__ g,
-                                                              unsigned short* __restrict__ gi, int64_t begin,
-                                                              int64_t n, float smin, float smax, int64_t C, int64_t K,
-                                                              const float* __restrict__ mins,
-                                                              const float* __restrict__ maxs)
-{
-    const int64_t stride = (int64_t) gridDim.x * kBlock;
-    for (int64_t i = begin + (int64_t) blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+        for (int k = 0; k < 8; ++k)
+            r[k] = ste16<IO>(a[k], b[k], mn, mx);
+        store_stream(r, reinterpret_cast<u16x8*>(gi) + i);
+    }
+    __device__ __forceinline__ void scalar(int64_t i) const
     {
         float mn = smin, mx = smax;
         if constexpr (CH)
@@ -148,58 +133,31 @@ __global__ __launch_bounds__(kBlock) void ste16_scalar_kernel(const unsigned sho
         }
         gi[i] = ste16<IO>(x[i], g[i], mn, mx);
     }
-}
+};
 
-bool aligned16(const void* a, const void* b, const void* c = nullptr)
+// vector part plus scalar tail (per-tensor), or everything scalar (K % 8 != 0)
+template <bool CH>
+bool vec_ok16(bool aligned, int64_t n, int64_t K)
 {
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) ==
-           0;
+    return aligned && (!CH || (K % 8 == 0 && n < (int64_t(1) << 32)));
 }
 
-// vector part over [0, nvec*8), scalar tail (per-tensor) or everything scalar (K % 8 != 0)
 template <int IO, bool CH, bool STO>
 void launch_qdq16(const void* in, void* out, int64_t n, const QdqParams& p, int64_t C, int64_t K, const float* table,
                   uint64_t seed, hipStream_t s)
 {
-    const bool vec_ok = aligned16(in, out) && (!CH || (K % 8 == 0 && n < (int64_t(1) << 32)));
-    int64_t nvec      = vec_ok ? n / 8 : 0;
-    if (nvec > 0)
-    {
-        ChannelMap16 map {FastDiv((uint32_t) (CH ? K : 1)), FastDiv((uint32_t) (CH ? C : 1)), (uint32_t) C};
-        qdq16_vec_kernel<IO, CH, STO><<<(unsigned) ceil_div(nvec, kBlock), kBlock, 0, s>>>(
-            reinterpret_cast<const u16x8*>(in), reinterpret_cast<u16x8*>(out), nvec, p, map, table, seed);
-        AIMET_LAUNCH_CHECK();
-    }
-    if (nvec * 8 < n)
-    {
-        qdq16_scalar_kernel<IO, CH, STO><<<stream_blocks(n - nvec * 8, kBlock), kBlock, 0, s>>>(
-            static_cast<const unsigned short*>(in), static_cast<unsigned short*>(out), nvec * 8, n, p, C, K, table,
-            seed);
-        AIMET_LAUNCH_CHECK();
-    }
+    Qdq16<IO, CH, STO> op {static_cast<const unsigned short*>(in), static_cast<unsigned short*>(out), p,
+                           ChannelMap(C, K), C, K, table, seed};
+    launch_stream<kLanes16, true>(op, n, vec_ok16<CH>(aligned16(in, out), n, K), s);
 }
 
 template <int IO, bool CH>
 void launch_ste16(const void* x, const void* g, void* gi, int64_t n, float mn, float mx, int64_t C, int64_t K,
                   const float* mins, const float* maxs, hipStream_t s)
 {
-    const bool vec_ok = aligned16(x, g, gi) && (!CH || (K % 8 == 0 && n < (int64_t(1) << 32)));
-    int64_t nvec      = vec_ok ? n / 8 : 0;
-    if (nvec > 0)
-    {
-        ChannelMap16 map {FastDiv((uint32_t) (CH ? K : 1)), FastDiv((uint32_t) (CH ? C : 1)), (uint32_t) C};
-        ste16_vec_kernel<IO, CH><<<(unsigned) ceil_div(nvec, kBlock), kBlock, 0, s>>>(
-            reinterpret_cast<const u16x8*>(x), reinterpret_cast<const u16x8*>(g), reinterpret_cast<u16x8*>(gi), nvec,
-            mn, mx, map, mins, maxs);
-        AIMET_LAUNCH_CHECK();
-    }
-    if (nvec * 8 < n)
-    {
-        ste16_scalar_kernel<IO, CH><<<stream_blocks(n - nvec * 8, kBlock), kBlock, 0, s>>>(
-            static_cast<const unsigned short*>(x), static_cast<const unsigned short*>(g),
-            static_cast<unsigned short*>(gi), nvec * 8, n, mn, mx, C, K, mins, maxs);
-        AIMET_LAUNCH_CHECK();
-    }
+    Ste16<IO, CH> op {static_cast<const unsigned short*>(x), static_cast<const unsigned short*>(g),
+                      static_cast<unsigned short*>(gi), mn, mx, ChannelMap(C, K), C, K, mins, maxs};
+    launch_stream<kLanes16, true>(op, n, vec_ok16<CH>(aligned16(x, g, gi), n, K), s);
 }
 
 template <bool CH>

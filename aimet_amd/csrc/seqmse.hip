@@ -12,9 +12,9 @@
 //     statistics, no H2D of n_cand tables, no synchronisation; the double divide and round/floor/
 //     ceil are IEEE on gfx950 and mse_core.hpp already runs getComputedEncodings there.
 //   * candidate_qdq: W is read once and stays in registers while the window's candidates are
-//     written with streaming stores: 4 + 4*count B/element instead of 8*count. One 16-B vector per
-//     lane, one tile per single-wave workgroup as channel_vec_kernel (qdq.hip), same element
-//     arithmetic (quantize_nearest / dequantize, IEEE divide).
+//     written with streaming stores: 4 + 4*count B/element instead of 8*count. The CandidateQdq
+//     op on the streaming skeleton of stream_map.hpp, at a fixed one wave per workgroup; the
+//     element arithmetic of qdq.hip (quantize_nearest / dequantize, IEEE divide).
 //   * recon_sums: sum over tokens of (xqwq - xw)^2 (or |.|) for every (candidate, channel) and
 //     sum xw^2 once, reading every xqwq element once. No float atomics: per-workgroup partials go
 //     to a workspace and a second small pass adds them in a fixed order, so the result is
@@ -27,6 +27,7 @@
 //     traffic).
 #include "common.hpp"
 #include "mse_core.hpp"
+#include "stream_map.hpp"
 
 #include <cmath>
 
@@ -36,9 +37,7 @@ namespace aimet_amd
 namespace
 {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-constexpr int kQdqLanes   = 64;   // candidate_qdq vector kernel: one wave per workgroup (qdq.hip's sweep)
+constexpr int kQdqLanes   = 64;   // CandidateQdq: fixed (stream_map.hpp: launch_stream)
 constexpr int kJT         = 4;    // candidates a lane accumulates at once in recon_sums
 constexpr int kReconBlock = 256;
 constexpr int kReconWaves = kReconBlock / 64;
@@ -116,48 +115,48 @@ __device__ __forceinline__ float qdq_nearest(float x, const QdqParams& p)
     return dequantize(quantize_nearest(x, p), p);
 }
 
-// K % 4 == 0: a 16-B vector never straddles two channels
-template <int LANES>
-__global__ __launch_bounds__(LANES) void candidate_qdq_vec_kernel(const f4* __restrict__ in, f4* __restrict__ out,
-                                                                  uint32_t nvec, FastDiv divK, int64_t C,
-                                                                  const float* __restrict__ tables, int count)
+// one load, `count` stores, candidate j's plane n elements after candidate j - 1's
+struct CandidateQdq
 {
-    const uint32_t i = blockIdx.x * LANES + threadIdx.x;
-    if (i >= nvec)
-        return;
-    const f4 v     = __builtin_nontemporal_load(in + i);
-    const float* t = tables + divK.div(i * 4);   // this channel's column of the first table
-    f4* o          = out + i;
-    for (int j = 0; j < count; ++j, t += 4 * C, o += nvec)
+    using index_t      = uint32_t;
+    using tail_index_t = uint32_t;
+    static constexpr int width = 4;
+    const float* __restrict__ in;
+    float* __restrict__ out;
+    uint32_t n;
+    FastDiv divK;
+    int64_t C;
+    const float* __restrict__ tables;
+    int count;
+    // K % 4 == 0: a 16-B vector never straddles two channels
+    __device__ __forceinline__ void vec(uint32_t i) const
     {
-        const QdqParams p {t[0], t[C], t[2 * C], t[3 * C]};
-        f4 r;
-        r.x = qdq_nearest(v.x, p);
-        r.y = qdq_nearest(v.y, p);
-        r.z = qdq_nearest(v.z, p);
-        r.w = qdq_nearest(v.w, p);
-        __builtin_nontemporal_store(r, o);
+        const f4 v     = load_stream(reinterpret_cast<const f4*>(in) + i);
+        const float* t = tables + divK.div(i * 4);   // this channel's column of the first table
+        f4* o          = reinterpret_cast<f4*>(out) + i;
+        for (int j = 0; j < count; ++j, t += 4 * C, o += n / 4)
+        {
+            const QdqParams p = load_params(t, C, int64_t(0));
+            f4 r;
+            r.x = qdq_nearest(v.x, p);
+            r.y = qdq_nearest(v.y, p);
+            r.z = qdq_nearest(v.z, p);
+            r.w = qdq_nearest(v.w, p);
+            store_stream(r, o);
+        }
     }
-}
-
-__global__ __launch_bounds__(kBlock) void candidate_qdq_scalar_kernel(const float* __restrict__ in,
-                                                                      float* __restrict__ out, uint32_t n,
-                                                                      FastDiv divK, int64_t C,
-                                                                      const float* __restrict__ tables, int count)
-{
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride)
+    __device__ __forceinline__ void scalar(uint32_t i) const
     {
         const float v  = in[i];
         const float* t = tables + divK.div(i);
         float* o       = out + i;
         for (int j = 0; j < count; ++j, t += 4 * C, o += n)
         {
-            const QdqParams p {t[0], t[C], t[2 * C], t[3 * C]};
-            *o = qdq_nearest(v, p);
+            const QdqParams p = load_params(t, C, int64_t(0));
+            *o                = qdq_nearest(v, p);
         }
     }
-}
+};
 
 // ---------------------------------------------------------------------------------------------
 // (c) reconstruction sums
@@ -409,11 +408,6 @@ __global__ __launch_bounds__(kBlock) void recon_fold_kernel(const float* __restr
         sig[i - N] = s;
 }
 
-inline bool aligned16(const void* a, const void* b)
-{
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
-}
-
 void check_recon_shape(int64_t outer, int64_t C, int64_t inner, int64_t count)
 {
     AIMET_REQUIRE(outer >= 0 && C > 0 && inner > 0 && count > 0, "invalid reconstruction shape");
@@ -466,17 +460,8 @@ int aimet_seqmse_candidate_qdq(const float* w, float* out, int64_t C, int64_t K,
         require_device_ptr(tables_dev, "tables");
         hipStream_t s  = as_stream(stream);
         const float* t = tables_dev + first * 4 * C;
-        const FastDiv divK((uint32_t) K);
-        if (K % 4 == 0 && aligned16(w, out))
-        {
-            const uint32_t nvec = (uint32_t) (n / 4);
-            candidate_qdq_vec_kernel<kQdqLanes><<<tile_grid(nvec, kQdqLanes), kQdqLanes, 0, s>>>(
-                reinterpret_cast<const f4*>(w), reinterpret_cast<f4*>(out), nvec, divK, C, t, (int) count);
-        }
-        else
-            candidate_qdq_scalar_kernel<<<stream_blocks(n, kBlock), kBlock, 0, s>>>(w, out, (uint32_t) n, divK, C, t,
-                                                                                    (int) count);
-        AIMET_LAUNCH_CHECK();
+        launch_stream<kQdqLanes, true>(CandidateQdq {w, out, (uint32_t) n, FastDiv((uint32_t) K), C, t, (int) count}, n,
+                                       K % 4 == 0 && aligned16(w, out), s);
     });
 }
 

@@ -804,7 +804,7 @@ def test_16bit_io_qdq_equals_upcast_path(dtype, rm):
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 def test_16bit_io_qdq_per_tensor_all_bit_patterns(dtype):
-    """Per-tensor nearest QDQ with 16-bit I/O (qdq16_vec_kernel, hoisted rounding threshold): every
+    """Per-tensor nearest QDQ with 16-bit I/O (the Qdq16 op, hoisted rounding threshold): every
     16-bit input pattern, tiled to a large tensor, equals upcast -> fp32 QDQ -> downcast."""
     from aimet_amd import _native
     from aimet_amd.tensor_quantizer import IO_DTYPES
@@ -825,7 +825,7 @@ def test_16bit_io_qdq_per_tensor_all_bit_patterns(dtype):
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 def test_16bit_io_qdq_per_channel_all_bit_patterns(dtype):
-    """Per-channel 16-bit QDQ (qdq16_vec_kernel, hoisted rounding threshold): every 16-bit input
+    """Per-channel 16-bit QDQ (the Qdq16 op, hoisted rounding threshold): every 16-bit input
     pattern in every channel, channels with dyadic deltas (exact half-integer quotients: the exact
     division path), zero / non-zero offsets, tiny and huge ranges, non-finite encodings; equals
     upcast -> fp32 per-channel QDQ (IEEE division) -> downcast bit for bit."""

@@ -4,6 +4,8 @@ or has just ended, on the vector path (16-B aligned) and the scalar path (views 
 element), with guard elements around every output. Nearest rounding is checked against the C oracle
 (oracle/dlq_oracle.c); stochastic rounding against the restatement below of the library's draw
 (common.hpp: uniform01 over the element index, which must not depend on the tile shape).
+The fp16 / bf16 I/O forms (a fixed 256 lanes of 8 elements) get the same treatment at their own tile
+edges: upcast on the host, the fp32 expectation, torch's CPU downcast.
 Needs an MI355X."""
 import ctypes
 import functools
@@ -79,20 +81,26 @@ def base(seed=0):
     return x
 
 
-def guarded_dev(payload, off):
-    """A device buffer [guard | off | payload | guard] filled with SENTINEL; returns (buffer, view)."""
-    n = payload.size if payload is not None and not isinstance(payload, int) else payload
-    buf = torch.full((2 * GUARD + off + n,), SENTINEL, dtype=torch.float32, device=DEV)
-    view = buf[GUARD + off:GUARD + off + n]
+def guarded_dev(payload, off, dtype=torch.float32):
+    """A device buffer [guard | off | payload | guard] filled with SENTINEL; returns (buffer, view).
+    payload: a float32 host array, a host tensor of `dtype`, or an element count."""
+    host = None
     if not isinstance(payload, int):
-        view.copy_(torch.from_numpy(np.array(payload, np.float32)))
+        host = payload if torch.is_tensor(payload) else torch.from_numpy(np.array(payload, np.float32))
+        assert host.dtype == dtype
+    n = payload if host is None else host.numel()
+    buf = torch.full((2 * GUARD + off + n,), SENTINEL, dtype=dtype, device=DEV)
+    view = buf[GUARD + off:GUARD + off + n]
+    if host is not None:
+        view.copy_(host)
     assert (view.data_ptr() % 16 == 0) == (off == 0)
     return buf, view
 
 
 def check_guards(buf, off, n, what):
-    h = buf.cpu().numpy()
-    assert np.all(h[:GUARD + off] == SENTINEL) and np.all(h[GUARD + off + n:] == SENTINEL), \
+    h = buf.cpu().float().numpy()
+    sentinel = torch.tensor(SENTINEL, dtype=buf.dtype).float().item()   # SENTINEL as the buffer's dtype holds it
+    assert np.all(h[:GUARD + off] == sentinel) and np.all(h[GUARD + off + n:] == sentinel), \
         "%s: wrote outside its output" % what
 
 
@@ -278,9 +286,128 @@ def test_ste_per_channel(lanes, C, K, outer):
     check_guards(obuf, 0, n, "STE per-channel %s" % ((C, K, outer),))
 
 
+# ---- fp16 / bf16 I/O (qdq16.hip: 8 elements per vector, a fixed 256 lanes) ----------------------
+# Expected values come from outside the library: the 16-bit input upcast on the host (exact), the
+# fp32 expectation of the sections above, and torch's CPU downcast.
+DTYPES16 = (torch.float16, torch.bfloat16)
+IDS16 = ["fp16", "bf16"]
+SIZES16 = (1, 7, 8, 9, 8 * 256 - 1, 8 * 256, 8 * 256 + 1, 16 * 256 + 7)
+CHANNEL_CASES16 = ((3, 4, 2), (3, 8, 1), (5, 16, 2), (7, 1032, 1), (64, 3, 1))   # K % 8 != 0: the scalar kernel
+
+
+def io_code(dtype):
+    from aimet_amd.tensor_quantizer import IO_DTYPES
+    return IO_DTYPES[dtype]
+
+
+def bits16(t):
+    """Bit patterns of a 16-bit tensor, NaNs compared as NaN-ness (as conftest.bits does)."""
+    t = t.detach().cpu().contiguous()
+    b = t.view(torch.int16).numpy().view(np.uint16).copy()
+    b[torch.isnan(t).numpy()] = 0x7FFF
+    return b
+
+
+def down(a, dtype):
+    return torch.from_numpy(np.array(a, np.float32)).to(dtype)
+
+
+def host16(a, dtype):
+    """(the 16-bit host tensor of a float32 array, its exact float32 upcast)."""
+    t = down(a, dtype)
+    up = t.float().numpy()
+    up.setflags(write=False)
+    return t, up
+
+
+@pytest.mark.parametrize("rm", [0, 1], ids=["nearest", "stochastic"])
+@pytest.mark.parametrize("dtype", DTYPES16, ids=IDS16)
+def test_per_tensor_16(dtype, rm):
+    mn, mx, delta, offset = filled()
+    for n in SIZES16:
+        for off in (0, 1):   # 16-B aligned (vector kernel + scalar tail) / offset by 2 bytes (scalar)
+            x16, xf = host16(base()[off:off + n], dtype)
+            if rm == 0:
+                want = O.qdq_per_tensor(xf, *ENC)
+            else:
+                want = stochastic_qdq(xf, mn, mx, delta, offset, SEED, np.arange(n, dtype=np.uint64))
+            _, x = guarded_dev(x16, off, dtype)
+            obuf, y = guarded_dev(n, off, dtype)
+            _native.call("aimet_qdq_per_tensor_16", x.data_ptr(), y.data_ptr(), n, io_code(dtype), enc_c(), rm, SEED,
+                         stream())
+            what = "n %d offset %d" % (n, off)
+            np.testing.assert_array_equal(bits16(y), bits16(down(want, dtype)), err_msg=what)
+            check_guards(obuf, off, n, what)
+
+
+@pytest.mark.parametrize("rm", [0, 1], ids=["nearest", "stochastic"])
+@pytest.mark.parametrize("C,K,outer", CHANNEL_CASES16)
+@pytest.mark.parametrize("dtype", DTYPES16, ids=IDS16)
+def test_per_channel_16(dtype, C, K, outer, rm):
+    flat, table = channel_case(C, K, outer)
+    n = flat.size
+    x16, xf = host16(flat, dtype)
+    want = bits16(down(want_per_channel(xf, table, C, K, outer, rm), dtype))
+    t = torch.from_numpy(np.array(table)).to(DEV)
+    for off in (0, 1):
+        _, x = guarded_dev(x16, off, dtype)
+        obuf, y = guarded_dev(n, off, dtype)
+        _native.call("aimet_qdq_per_channel_16", x.data_ptr(), y.data_ptr(), outer, C, K, io_code(dtype),
+                     t.data_ptr(), rm, SEED, stream())
+        what = "per-channel %s offset %d" % ((C, K, outer), off)
+        np.testing.assert_array_equal(bits16(y), want, err_msg=what)
+        check_guards(obuf, off, n, what)
+
+
+def ste_want_16(xf, gf, mn, mx, dtype):
+    """grad * (min <= float(x) <= max) on the upcast operands, downcast by torch on the CPU."""
+    with np.errstate(invalid="ignore"):
+        return down(gf * ((mn <= xf) & (xf <= mx)).astype(np.float32), dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES16, ids=IDS16)
+def test_ste_per_tensor_16(dtype):
+    mn, mx = np.float32(-2.5), np.float32(4.0)
+    for n in SIZES16:
+        for off in (0, 1):
+            x16, xf = host16(base()[off:off + n], dtype)
+            g16, gf = host16(base(1)[off:off + n], dtype)
+            _, x = guarded_dev(x16, off, dtype)
+            _, g = guarded_dev(g16, off, dtype)
+            obuf, gi = guarded_dev(n, off, dtype)
+            _native.call("aimet_ste_backward_16", x.data_ptr(), g.data_ptr(), gi.data_ptr(), 1, 1, n, io_code(dtype),
+                         None, None, float(mn), float(mx), stream())
+            what = "n %d offset %d" % (n, off)
+            np.testing.assert_array_equal(bits16(gi), bits16(ste_want_16(xf, gf, mn, mx, dtype)), err_msg=what)
+            check_guards(obuf, off, n, what)
+
+
+@pytest.mark.parametrize("C,K,outer", CHANNEL_CASES16)
+@pytest.mark.parametrize("dtype", DTYPES16, ids=IDS16)
+def test_ste_per_channel_16(dtype, C, K, outer):
+    flat, table = channel_case(C, K, outer)
+    n = flat.size
+    x16, xf = host16(flat, dtype)
+    g16, gf = host16(base(1)[:n], dtype)
+    ch = (np.arange(n) // K) % C
+    want = bits16(ste_want_16(xf, gf, table[0][ch], table[1][ch], dtype))
+    mins = torch.from_numpy(np.array(table[0])).to(DEV)
+    maxs = torch.from_numpy(np.array(table[1])).to(DEV)
+    for off in (0, 1):
+        _, x = guarded_dev(x16, off, dtype)
+        _, g = guarded_dev(g16, off, dtype)
+        obuf, gi = guarded_dev(n, off, dtype)
+        _native.call("aimet_ste_backward_16", x.data_ptr(), g.data_ptr(), gi.data_ptr(), outer, C, K, io_code(dtype),
+                     mins.data_ptr(), maxs.data_ptr(), 0.0, 0.0, stream())
+        what = "STE per-channel %s offset %d" % ((C, K, outer), off)
+        np.testing.assert_array_equal(bits16(gi), want, err_msg=what)
+        check_guards(obuf, off, n, what)
+
+
 # ---- the kernels of the same form in other files -------------------------------------------------
 def test_fp16_round_trip(lanes):
-    """aimet_qdq_fp16 (fp16_vec_kernel + its scalar tail): float -> half -> float, as the oracle."""
+    """aimet_qdq_fp16 (the Fp16RoundTrip op: vector kernel + scalar tail): float -> half -> float, as
+    the oracle."""
     for n in sizes(lanes):
         for off in (0, 1):
             xh = base()[off:off + n]

@@ -11,7 +11,7 @@ import glob
 import os
 import sys
 
-QDQ = "tensor_vec_kernel"
+QDQ = "TensorQdq"   # stream_vec_kernel<LANES, TensorQdq<...>> (tensor_vec_kernel in traces up to round 11)
 
 
 def trace_rows(d):
