@@ -52,7 +52,6 @@ struct AdaChannel
     }
 };
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // expf as torch's CPU vector code computes it (ATen Vectorized<float>::exp = Sleef expf_u10):
 // q = rint(d * log2(e)); s = d - q*ln2 in two FMA steps (Cody-Waite); a degree-6 polynomial in

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "aimet_amd.h"
+#include "vec_types.hpp"
 
 namespace aimet_amd
 {

@@ -27,13 +27,13 @@
 #include <hip/hip_runtime.h>
 
 #include "fast_pow_tab.hpp"
+#include "vec_types.hpp"
 
 namespace aimet_amd
 {
 namespace
 {
 
-typedef float f4t __attribute__((ext_vector_type(4)));
 typedef float f2t __attribute__((ext_vector_type(2)));
 
 // the tables in LDS: every kernel that evaluates the fast pow fills them first (pow_tab_fill or
@@ -94,7 +94,7 @@ __device__ __forceinline__ LnSplit ln01(float x)
     const int k     = __builtin_amdgcn_frexp_expf(x);
     const float m   = __builtin_amdgcn_frexp_mantf(x);   // [0.5, 1)
     const uint32_t j = (__float_as_uint(m) >> 16) & 127u;
-    const f4t e     = *reinterpret_cast<const f4t*>(g_pow_tab.ln[j]);   // one 16-B LDS read
+    const f4 e      = *reinterpret_cast<const f4*>(g_pow_tab.ln[j]);   // one 16-B LDS read
     const float r   = __builtin_fmaf(m, e.x, -1.0f);
     float t         = __builtin_fmaf(r, -0.25f, 0.333333343f);
     t               = __builtin_fmaf(r, t, -0.5f);

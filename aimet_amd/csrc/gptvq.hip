@@ -46,7 +46,6 @@ constexpr int64_t kTwo31  = int64_t(1) << 31;
 std::atomic<int> g_update_layout {0};
 
 typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 template <int D>
 __device__ __forceinline__ void load_vec(const float* p, float* v, int d_rt)

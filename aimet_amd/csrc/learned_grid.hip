@@ -12,6 +12,18 @@
 // asymmetric: grad_min = -(A-B)/steps + max * steps/(max-min)^2 * delta*D ; grad_max = (A-B)/steps - min * (...)
 // symmetric:  grad_max = (A - B) / floor(steps/2), grad_min = -grad_max
 // (assembled from the C-vectors on the torch side). Float32; torch.round = round-half-even.
+//
+// Layout of this file. Device side: the element arithmetic (lg_qdq*, lg_bwd_term_m, lg_quot), then
+// the backward's pieces, each written once -- LgIo<IO> (how 8 consecutive elements are loaded,
+// converted and stored: float32, fp16 or bf16), lg_bwd_full_tile and lg_bwd_elem_tile (a per-tensor
+// tile on the vector path and element by element, the same summation order), lg_bwd_quad (a quad
+// of the per-channel kernels), lg_two_buffers (the pipelined tile loop of the 16-bit kernels) and
+// lg_publish / store_sums (every {A, B, D} triple) -- and the kernels, which keep only their
+// schedules and element -> lane -> workgroup maps. Host side: one launcher per form of the
+// backward (backward_tensor<IO>, backward_tiles<GIO>, and the two channel forms inside
+// aimet_lg_backward), backward_begin (validation and the empty call) and lg_tile_form (the tile
+// form's eligibility) shared by the three C entries; launch_lg_encodings for every launch of
+// lg_encodings_kernel, with enc_of the one place that turns (bw, sym, strict, unsign) into a grid.
 #include "common.hpp"
 #include <atomic>
 #include <cmath>
@@ -20,25 +32,24 @@
 #include <type_traits>
 #include <utility>
 #include "io16.hpp"
+#include "stream_map.hpp"
 
 namespace aimet_amd
 {
 namespace
 {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
 constexpr int kLgUnroll = 4;
 
-struct LgChannel
+// ChannelMap with a per-tensor shortcut: lg_fwd_kernel also serves C == 1 (one encoding, K = n),
+// where the shortcut is one scalar branch instead of two multiply-high divisions per quad.
+// ChannelMap alone gives the same channel (0) but not that kernel's machine code, so this stays.
+struct LgChannel : ChannelMap
 {
-    FastDiv divK, divC;
-    uint32_t C;
+    LgChannel(int64_t C_, int64_t K_) : ChannelMap(C_, K_ > 0 ? K_ : 1) {}
     __device__ __forceinline__ uint32_t channel(uint32_t i) const
     {
-        if (C == 1)
-            return 0;
-        uint32_t row = divK.div(i);
-        return row - divC.div(row) * C;
+        return C == 1 ? 0 : ChannelMap::channel(i);
     }
 };
 
@@ -124,6 +135,7 @@ __device__ __forceinline__ void lg_qdq_n(const float* x, float d, float o, float
 }
 
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
 // torch's maximum / minimum: a NaN operand is returned
 __device__ __forceinline__ float t_maximum(float a, float b)
@@ -197,11 +209,11 @@ template <int OUT>
 __device__ __forceinline__ void lg_store4(void* __restrict__ y, uint32_t q, f4 r)
 {
     if constexpr (OUT == IO_F32)
-        __builtin_nontemporal_store(r, static_cast<f4*>(y) + q);
+        store_stream(r, static_cast<f4*>(y) + q);
     else
     {
         const u16x4 h = {from_f32<OUT>(r.x), from_f32<OUT>(r.y), from_f32<OUT>(r.z), from_f32<OUT>(r.w)};
-        __builtin_nontemporal_store(h, static_cast<u16x4*>(y) + q);
+        store_stream(h, static_cast<u16x4*>(y) + q);
     }
 }
 
@@ -229,7 +241,7 @@ __global__ __launch_bounds__(LANES) void lg_fwd_kernel(const float* __restrict__
 #pragma unroll
         for (int u = 0; u < Q; ++u)
             if (q0 + u * LANES < nq)
-                v[u] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(x) + q0 + u * LANES);
+                v[u] = load_stream(reinterpret_cast<const f4*>(x) + q0 + u * LANES);
         uint32_t pc = 0xffffffffu;
         float d = 0.0f, o = 0.0f, rd = 0.0f;
 #pragma unroll
@@ -291,10 +303,10 @@ template <int GIO>
 __device__ __forceinline__ f4 load_grad4(const void* __restrict__ g, uint32_t i)
 {
     if constexpr (GIO == IO_F32)
-        return __builtin_nontemporal_load(static_cast<const f4*>(g) + i);
+        return load_stream(static_cast<const f4*>(g) + i);
     else
     {
-        const u16x4 h = __builtin_nontemporal_load(static_cast<const u16x4*>(g) + i);
+        const u16x4 h = load_stream(static_cast<const u16x4*>(g) + i);
         return f4 {to_f32<GIO>(h.x), to_f32<GIO>(h.y), to_f32<GIO>(h.z), to_f32<GIO>(h.w)};
     }
 }
@@ -433,6 +445,22 @@ __device__ __forceinline__ Sums block_reduce(Sums s)
     return r;
 }
 
+// every {A, B, D} triple the kernels write: a channel's sums, or a partial for a fold
+__device__ __forceinline__ void store_sums(float* p, const Sums& t)
+{
+    p[0] = t.a;
+    p[1] = t.b;
+    p[2] = t.d;
+}
+
+// the workgroup's triple (its lanes' sums through block_reduce), stored by thread 0
+__device__ __forceinline__ void lg_publish(const Sums& s, float* p)
+{
+    const Sums t = block_reduce(s);
+    if (threadIdx.x == 0)
+        store_sums(p, t);
+}
+
 // the encoding gradients of channel c from its sums {A, B, D} (asymmetric / symmetric_gradients,
 // the reference's torch expressions element by element); gmin == nullptr: not requested
 struct LgRange
@@ -502,20 +530,10 @@ __device__ __forceinline__ void fold_partials(const float* __restrict__ partial,
     Sums t = block_reduce(s);
     if (threadIdx.x == 0)
     {
-        sums[0] = t.a;
-        sums[1] = t.b;
-        sums[2] = t.d;
+        store_sums(sums, t);
         if (range.gmin)
             range_grads_one(t.a, t.b, t.d, 0, range);
     }
-}
-
-// a tile's partial triple (folded by the next launch)
-__device__ __forceinline__ void store_sums(float* p, const Sums& t)
-{
-    p[0] = t.a;
-    p[1] = t.b;
-    p[2] = t.d;
 }
 
 // per-tensor (C == 1), tile form: workgroup b owns the kLgTile consecutive elements
@@ -536,9 +554,134 @@ __device__ __forceinline__ int64_t lg_tile_elem(int64_t base, int u, int k)
     return base + ((int64_t) u * kBlock + threadIdx.x) * 8 + k;
 }
 
+// How the per-tensor backward reads and writes a tensor of float32 (IO_F32), fp16 or bf16: a
+// lane's group u of the tile at `base` -- the 8 consecutive elements from lg_tile_elem(base, u, 0)
+// -- is one streamed 16-B vector of 16-bit values, or two of floats, held as loaded (regs_t) until
+// unpack() makes them 8 floats (the upcast is exact); store() converts 8 floats back (torch's
+// rounding, io16.hpp) and streams them out. store() forms its address after the conversion: handed
+// the address, the 16-bit kernels came out two VGPRs larger. up / down: one element, for the
+// element path.
+template <int IO>
+struct LgIo
+{
+    typedef unsigned short elem_t;
+    typedef u16x8 regs_t;
+    static __device__ __forceinline__ float up(elem_t v) { return to_f32<IO>(v); }
+    static __device__ __forceinline__ elem_t down(float v) { return from_f32<IO>(v); }
+    static __device__ __forceinline__ regs_t load(const elem_t* p, int64_t base, int u)
+    {
+        return load_stream(reinterpret_cast<const u16x8*>(p) + lg_tile_elem(base, u, 0) / 8);
+    }
+    static __device__ __forceinline__ void unpack(const regs_t& r, float* f)
+    {
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            f[k] = to_f32<IO>(r[k]);
+    }
+    static __device__ __forceinline__ void store(elem_t* p, int64_t base, int u, const float* f)
+    {
+        u16x8 h;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            h[k] = from_f32<IO>(f[k]);
+        store_stream(h, reinterpret_cast<u16x8*>(p) + lg_tile_elem(base, u, 0) / 8);
+    }
+};
+template <>
+struct LgIo<IO_F32>
+{
+    typedef float elem_t;
+    struct regs_t
+    {
+        f4 lo, hi;
+    };
+    static __device__ __forceinline__ float up(float v) { return v; }
+    static __device__ __forceinline__ float down(float v) { return v; }
+    static __device__ __forceinline__ regs_t load(const float* p, int64_t base, int u)
+    {
+        const int64_t q = lg_tile_elem(base, u, 0) / 4;
+        return regs_t {load_stream(reinterpret_cast<const f4*>(p) + q),
+                       load_stream(reinterpret_cast<const f4*>(p) + q + 1)};
+    }
+    static __device__ __forceinline__ void unpack(const regs_t& r, float* f)
+    {
+        f[0] = r.lo.x, f[1] = r.lo.y, f[2] = r.lo.z, f[3] = r.lo.w;
+        f[4] = r.hi.x, f[5] = r.hi.y, f[6] = r.hi.z, f[7] = r.hi.w;
+    }
+    static __device__ __forceinline__ void store(float* p, int64_t base, int u, const float* f)
+    {
+        const int64_t q = lg_tile_elem(base, u, 0) / 4;
+        const f4 r0 = {f[0], f[1], f[2], f[3]}, r1 = {f[4], f[5], f[6], f[7]};
+        store_stream(r0, reinterpret_cast<f4*>(p) + q);
+        store_stream(r1, reinterpret_cast<f4*>(p) + q + 1);
+    }
+};
+
+// one full tile's x and gradient as loaded: STEPS groups per lane
+template <int IO, int STEPS>
+struct LgTileRegs
+{
+    typename LgIo<IO>::regs_t x[STEPS], g[STEPS];
+};
+
+template <int IO, int STEPS>
+__device__ __forceinline__ void lg_bwd_load(const typename LgIo<IO>::elem_t* x,
+                                            const typename LgIo<IO>::elem_t* g, int64_t base,
+                                            LgTileRegs<IO, STEPS>& r)
+{
+#pragma unroll
+    for (int u = 0; u < STEPS; ++u)
+    {
+        r.x[u] = LgIo<IO>::load(x, base, u);
+        r.g[u] = LgIo<IO>::load(g, base, u);
+    }
+}
+
+// A full tile of an encoding lg_fast_enc accepts, from its loaded registers: the lane's sums in
+// (u, element) order, grad_x stored when requested.
+template <int IO, int STEPS, int MODE>
+__device__ __forceinline__ void lg_bwd_full_tile(const LgTileRegs<IO, STEPS>& v,
+                                                 typename LgIo<IO>::elem_t* gx, int64_t base, float dl,
+                                                 float o, float steps, float rcp, Sums& s)
+{
+#pragma unroll
+    for (int u = 0; u < STEPS; ++u)
+    {
+        float r[8], xv[8], gv[8];
+        LgIo<IO>::unpack(v.x[u], xv);
+        LgIo<IO>::unpack(v.g[u], gv);
+        lg_bwd_elems_fast<8, MODE>(xv, gv, dl, o, steps, rcp, r, s);
+        if (gx)
+            LgIo<IO>::store(gx, base, u, r);
+    }
+}
+
+// Any tile element by element -- the last (partial) tile, unaligned pointers or an encoding for
+// the division: the lane's sums in the same (u, element) order as lg_bwd_full_tile
+// (tests/test_gpu_parity.py compares the two paths bit for bit).
+template <int IO, int STEPS, int MODE>
+__device__ __forceinline__ void lg_bwd_elem_tile(const typename LgIo<IO>::elem_t* x,
+                                                 const typename LgIo<IO>::elem_t* g,
+                                                 typename LgIo<IO>::elem_t* gx, int64_t base, int64_t n,
+                                                 float dl, float o, float steps, float rcp, Sums& s)
+{
+    for (int u = 0; u < STEPS; ++u)
+        for (int k = 0; k < 8; ++k)
+        {
+            const int64_t e = lg_tile_elem(base, u, k);
+            if (e >= n)
+                break;
+            float r;
+            lg_bwd_elem(LgIo<IO>::up(x[e]), LgIo<IO>::up(g[e]), dl, o, steps, rcp, r, s, MODE);
+            if (gx)
+                gx[e] = LgIo<IO>::down(r);
+        }
+}
+
 // Tiles per launch: tile b is processed by workgroup b % gridDim.x (grid = the tile count unless
 // a tuning cap is set); its partial triple goes to sums[3 * b], so the fold sees the same partials
-// in the same order whatever the grid.
+// in the same order whatever the grid. The schedule: one tile per trip, every load of the tile
+// before any arithmetic.
 template <int STEPS, int MODE>
 __global__ __launch_bounds__(kBlock) void lg_bwd_tensor_kernel(const float* __restrict__ x,
                                                                const float* __restrict__ g, float* __restrict__ gx,
@@ -555,53 +698,13 @@ __global__ __launch_bounds__(kBlock) void lg_bwd_tensor_kernel(const float* __re
         Sums s {0, 0, 0};
         if (fast && vec && base + kTile <= n)
         {
-            f4 a[STEPS][2], b[STEPS][2];
-#pragma unroll
-            for (int u = 0; u < STEPS; ++u)
-            {
-                const int64_t q = lg_tile_elem(base, u, 0) / 4;
-                a[u][0] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(x) + q);
-                a[u][1] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(x) + q + 1);
-                b[u][0] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(g) + q);
-                b[u][1] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(g) + q + 1);
-            }
-#pragma unroll
-            for (int u = 0; u < STEPS; ++u)
-            {
-                float r[8];
-                const float xv[8] = {a[u][0].x, a[u][0].y, a[u][0].z, a[u][0].w,
-                                     a[u][1].x, a[u][1].y, a[u][1].z, a[u][1].w};
-                const float gv[8] = {b[u][0].x, b[u][0].y, b[u][0].z, b[u][0].w,
-                                     b[u][1].x, b[u][1].y, b[u][1].z, b[u][1].w};
-                lg_bwd_elems_fast<8, MODE>(xv, gv, dl, o, steps, rcp, r, s);
-                if (gx)
-                {
-                    const int64_t q = lg_tile_elem(base, u, 0) / 4;
-                    const f4 r0 = {r[0], r[1], r[2], r[3]}, r1 = {r[4], r[5], r[6], r[7]};
-                    __builtin_nontemporal_store(r0, reinterpret_cast<f4*>(gx) + q);
-                    __builtin_nontemporal_store(r1, reinterpret_cast<f4*>(gx) + q + 1);
-                }
-            }
+            LgTileRegs<IO_F32, STEPS> v;
+            lg_bwd_load(x, g, base, v);
+            lg_bwd_full_tile<IO_F32, STEPS, MODE>(v, gx, base, dl, o, steps, rcp, s);
         }
         else
-        {
-            // the last (partial) tile, unaligned pointers or an encoding for the division: element
-            // by element, the same order
-            for (int u = 0; u < STEPS; ++u)
-                for (int k = 0; k < 8; ++k)
-                {
-                    const int64_t e = lg_tile_elem(base, u, k);
-                    if (e >= n)
-                        break;
-                    float r;
-                    lg_bwd_elem(x[e], g[e], dl, o, steps, rcp, r, s, MODE);
-                    if (gx)
-                        gx[e] = r;
-                }
-        }
-        Sums t = block_reduce(s);
-        if (threadIdx.x == 0)
-            store_sums(sums + 3 * tile, t);
+            lg_bwd_elem_tile<IO_F32, STEPS, MODE>(x, g, gx, base, n, dl, o, steps, rcp, s);
+        lg_publish(s, sums + 3 * tile);
     }
 }
 
@@ -672,13 +775,25 @@ __global__ __launch_bounds__(kBlock) void lg_bwd_channel_kernel(const float* __r
                     gx[base + k] = v;
             }
         }
-        Sums t = block_reduce(s);
-        if (threadIdx.x == 0)
-        {
-            sums[3 * c + 0] = t.a;
-            sums[3 * c + 1] = t.b;
-            sums[3 * c + 2] = t.d;
-        }
+        lg_publish(s, sums + 3 * c);
+    }
+}
+
+// One quad of the per-channel vector kernels, x and the gradient as loaded (lg_bwd_elems: the
+// division where the encoding needs it); its grad_x is streamed to `out` when grad_x is requested.
+// `out` is the address the caller's loads already formed, meaningful only then. (The quad of
+// grad_x is packed inside that test: packed before it, the compiler pairs the mask products into
+// v_pk_mul_f32 and the kernels need two more VGPRs.)
+__device__ __forceinline__ void lg_bwd_quad(f4 a, f4 b, bool store, f4* out, float dl, float o, float steps, float rcp,
+                                            int mode, Sums& s)
+{
+    float rr[4];
+    const float xv[4] = {a.x, a.y, a.z, a.w}, gv[4] = {b.x, b.y, b.z, b.w};
+    lg_bwd_elems<4>(xv, gv, dl, o, steps, rcp, rr, s, mode);
+    if (store)
+    {
+        f4 rv = {rr[0], rr[1], rr[2], rr[3]};
+        store_stream(rv, out);
     }
 }
 
@@ -711,41 +826,18 @@ __global__ __launch_bounds__(kBlock) void lg_bwd_channel_vec_kernel(const f4* __
                 const int64_t jj = j < Q ? j : Q - 1;   // clamped (neither summed nor stored)
                 const int64_t r  = outer == 1 ? 0 : divK4.div((uint32_t) jj);
                 idx[u]           = (r * C + c) * K4 + (jj - r * K4);
-                a[u]             = __builtin_nontemporal_load(x + idx[u]);
-                b[u]             = __builtin_nontemporal_load(g + idx[u]);
+                a[u]             = load_stream(x + idx[u]);
+                b[u]             = load_stream(g + idx[u]);
             }
 #pragma unroll
             for (int u = 0; u < kLgUnroll; ++u)
             {
                 if (j0 + u * step >= Q)
                     break;
-                float rr[4];
-                const float xv[4] = {a[u].x, a[u].y, a[u].z, a[u].w}, gv[4] = {b[u].x, b[u].y, b[u].z, b[u].w};
-                lg_bwd_elems<4>(xv, gv, dl, o, steps, rcp, rr, s, mode);
-                if (gx)
-                {
-                    f4 rv = {rr[0], rr[1], rr[2], rr[3]};
-                    __builtin_nontemporal_store(rv, gx + idx[u]);
-                }
+                lg_bwd_quad(a[u], b[u], gx != nullptr, gx + idx[u], dl, o, steps, rcp, mode, s);
             }
         }
-        Sums t = block_reduce(s);
-        if (threadIdx.x == 0)
-        {
-            if (splits == 1)
-            {
-                sums[3 * c + 0] = t.a;
-                sums[3 * c + 1] = t.b;
-                sums[3 * c + 2] = t.d;
-            }
-            else
-            {
-                const int64_t p = c * splits + blockIdx.y;
-                sums[3 * p + 0] = t.a;
-                sums[3 * p + 1] = t.b;
-                sums[3 * p + 2] = t.d;
-            }
-        }
+        lg_publish(s, sums + 3 * (splits == 1 ? c : c * splits + blockIdx.y));
     }
 }
 
@@ -769,29 +861,14 @@ __global__ __launch_bounds__(kBlock) void lg_bwd_tile_kernel(const f4* __restric
 #pragma unroll
     for (int u = 0; u < U; ++u)
     {
-        a[u] = __builtin_nontemporal_load(x + q0 + u * kBlock + threadIdx.x);
+        a[u] = load_stream(x + q0 + u * kBlock + threadIdx.x);
         b[u] = load_grad4<GIO>(g, q0 + u * kBlock + threadIdx.x);
     }
     Sums s {0, 0, 0};
 #pragma unroll
     for (int u = 0; u < U; ++u)
-    {
-        float rr[4];
-        const float xv[4] = {a[u].x, a[u].y, a[u].z, a[u].w}, gv[4] = {b[u].x, b[u].y, b[u].z, b[u].w};
-        lg_bwd_elems<4>(xv, gv, dl, o, steps, rcp, rr, s, mode);
-        if (gx)
-        {
-            f4 rv = {rr[0], rr[1], rr[2], rr[3]};
-            __builtin_nontemporal_store(rv, gx + q0 + u * kBlock + threadIdx.x);
-        }
-    }
-    Sums t = block_reduce(s);
-    if (threadIdx.x == 0)
-    {
-        partial[3 * blockIdx.x + 0] = t.a;
-        partial[3 * blockIdx.x + 1] = t.b;
-        partial[3 * blockIdx.x + 2] = t.d;
-    }
+        lg_bwd_quad(a[u], b[u], gx != nullptr, gx + q0 + u * kBlock + threadIdx.x, dl, o, steps, rcp, mode, s);
+    lg_publish(s, partial + 3 * blockIdx.x);
 }
 
 // sums[c] = sum over the rows r of channel c and their workgroups w (in that order)
@@ -801,20 +878,18 @@ __global__ __launch_bounds__(kBlock) void lg_bwd_tile_fold(const float* __restri
     const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
     if (c >= C)
         return;
-    float a = 0, b = 0, d = 0;
+    Sums s {0, 0, 0};
     for (uint32_t r = 0; r < outer; ++r)
         for (uint32_t w = 0; w < per_row; ++w)
         {
             const float* p = partial + 3 * ((size_t) (r * C + c) * per_row + w);
-            a += p[0];
-            b += p[1];
-            d += p[2];
+            s.a += p[0];
+            s.b += p[1];
+            s.d += p[2];
         }
-    sums[3 * c + 0] = a;
-    sums[3 * c + 1] = b;
-    sums[3 * c + 2] = d;
+    store_sums(sums + 3 * c, s);
     if (range.gmin)
-        range_grads_one(a, b, d, c, range);
+        range_grads_one(s.a, s.b, s.d, c, range);
 }
 
 // ---- fp16 / bf16 I/O, per tensor (C == 1): the conversions in registers ------------------------
@@ -823,8 +898,6 @@ __global__ __launch_bounds__(kBlock) void lg_bwd_tile_fold(const float* __restri
 // lg_bwd_tensor_kernel (quads, then the tail), and the downcast is torch's (io16.hpp). 4 B/elem
 // forward and 6 B/elem backward instead of 20 and 24 for the three-pass chains.
 
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
 // lg_fwd16_kernel's default shape: kLgFwd16Vecs 16-B vectors (8 elements) per lane and tile,
 // kLgFwd16Grid workgroups looping over the tiles (other shapes measured slower, profiles/r03/
 // lg16_kernel_stats.csv, profiles/r04/lg16_*.jsonl)
@@ -832,32 +905,45 @@ constexpr int kLgFwd16Vecs     = 1;
 constexpr int64_t kLgFwd16Grid  = 2048;   // workgroups: 8 per CU, one resident round
 constexpr int64_t kLgFwd16Tile = (int64_t) kBlock * 8 * kLgFwd16Vecs;
 
-// 16-B loads / stores of the 16-bit kernels: nontemporal (NT, the streaming default) or through
-// the caches (measured no faster for activations still resident in the MALL, profiles/r04)
-template <bool NT>
-__device__ __forceinline__ u16x8 ld16(const u16x8* p)
-{
-    if constexpr (NT)
-        return __builtin_nontemporal_load(p);
-    else
-        return *p;
-}
-template <bool NT>
-__device__ __forceinline__ void st16(u16x8 v, u16x8* p)
-{
-    if constexpr (NT)
-        __builtin_nontemporal_store(v, p);
-    else
-        *p = v;
-}
-
-template <int IO, int V, int BLOCK, bool NT>
+// The 16-bit kernels stream their 16-B loads and stores like every other kernel here (through the
+// caches measured no faster for activations still resident in the MALL, profiles/r04).
+template <int V, int BLOCK>
 __device__ __forceinline__ void lg_fwd16_load(const unsigned short* __restrict__ x, int64_t tile, u16x8* v)
 {
     constexpr int64_t kTile = (int64_t) BLOCK * 8 * V;
 #pragma unroll
     for (int u = 0; u < V; ++u)
-        v[u] = ld16<NT>(reinterpret_cast<const u16x8*>(x) + tile * kTile / 8 + u * BLOCK + threadIdx.x);
+        v[u] = load_stream(reinterpret_cast<const u16x8*>(x) + tile * kTile / 8 + u * BLOCK + threadIdx.x);
+}
+
+// The pipelined tile loop of the 16-bit kernels: workgroup b takes the full tiles b, b + grid, ...
+// below nfull, `cur` already holding the first one. Two register buffers in turn (no copy of the
+// next tile's registers, which made the compiler wait for its loads at the end of every tile); the
+// next tile's loads are unconditional -- the last tile reloads itself, unused -- so the same
+// number of loads is outstanding on every path and the wait at each tile's first use leaves them
+// in flight. load(tile, buffer) issues a tile's loads, compute(buffer, tile) consumes them.
+// Returns the first tile not processed.
+template <class Buf, class Load, class Compute>
+__device__ __forceinline__ int64_t lg_two_buffers(int64_t tile, int64_t nfull, Buf& cur, Buf& nxt, Load load,
+                                                  Compute compute)
+{
+    if (tile < nfull)
+        for (;;)
+        {
+            int64_t tn = tile + gridDim.x < nfull ? tile + gridDim.x : tile;
+            load(tn, nxt);
+            compute(cur, tile);
+            tile += gridDim.x;
+            if (tile >= nfull)
+                break;
+            tn = tile + gridDim.x < nfull ? tile + gridDim.x : tile;
+            load(tn, cur);
+            compute(nxt, tile);
+            tile += gridDim.x;
+            if (tile >= nfull)
+                break;
+        }
+    return tile;
 }
 
 // Workgroup b takes tiles b, b + grid, ... (grid capped near one resident wave of workgroups per
@@ -865,7 +951,7 @@ __device__ __forceinline__ void lg_fwd16_load(const unsigned short* __restrict__
 // keeps its 16-B loads in flight through its own arithmetic (a wave that loaded, waited and then
 // computed left the memory pipe idle during the ~20 VALU per element). Full tiles only; the
 // partial last tile, unaligned pointers and encodings for the division take the element loop.
-template <int IO, int V, int BLOCK, bool NT = true>
+template <int IO, int V, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void lg_fwd16_kernel(const unsigned short* __restrict__ x,
                                                          unsigned short* __restrict__ y, int64_t n,
                                                          const float* __restrict__ delta,
@@ -877,9 +963,9 @@ __global__ __launch_bounds__(BLOCK) void lg_fwd16_kernel(const unsigned short* _
     // small call the two latencies in a row were most of the kernel)
     const int64_t nvec = vec ? n / kTile : 0;
     int64_t tile       = blockIdx.x;
-    u16x8 cur[V];
+    u16x8 cur[V], nxt[V];
     if (tile < nvec)
-        lg_fwd16_load<IO, V, BLOCK, NT>(x, tile, cur);
+        lg_fwd16_load<V, BLOCK>(x, tile, cur);
     float d, o;
     // element 0's thread (tile 0 is workgroup 0's first) stores the encoding
     enc.get(0, blockIdx.x == 0 && threadIdx.x == 0 ? 0u : 1u, delta, offset, d, o);
@@ -887,9 +973,9 @@ __global__ __launch_bounds__(BLOCK) void lg_fwd16_kernel(const unsigned short* _
     const float xmax = 0x1p59f * __builtin_fabsf(d);
     const bool fast  = lg_fast_enc(o, rd);
     const int64_t nfull = fast ? nvec : 0;
-    if (tile < nfull)
-    {
-        auto compute = [&](const u16x8 (&v)[V], int64_t t) {
+    tile = lg_two_buffers(
+        tile, nfull, cur, nxt, [&](int64_t t, u16x8 (&v)[V]) { lg_fwd16_load<V, BLOCK>(x, t, v); },
+        [&](const u16x8 (&v)[V], int64_t t) {
 #pragma unroll
             for (int u = 0; u < V; ++u)
             {
@@ -903,55 +989,22 @@ __global__ __launch_bounds__(BLOCK) void lg_fwd16_kernel(const unsigned short* _
                     const float yq = lg_qdq_fast(xf, d, o, steps, rd, xmax);
                     r[k] = xf != xf ? from_f32<IO>(quiet_nan(xf)) : from_f32<IO, false>(yq);
                 }
-                st16<NT>(r, reinterpret_cast<u16x8*>(y) + t * kTile / 8 + u * BLOCK + threadIdx.x);
+                store_stream(r, reinterpret_cast<u16x8*>(y) + t * kTile / 8 + u * BLOCK + threadIdx.x);
             }
-        };
-        // two register buffers in turn (no copy of the next tile's registers, which made the
-        // compiler wait for its loads at the end of every tile); the next tile's loads are
-        // unconditional -- the last tile reloads itself, unused -- so the same number of loads is
-        // outstanding on every path and the wait at each tile's first use leaves them in flight
-        u16x8 nxt[V];
-        for (;;)
-        {
-            int64_t tn = tile + gridDim.x < nfull ? tile + gridDim.x : tile;
-            lg_fwd16_load<IO, V, BLOCK, NT>(x, tn, nxt);
-            compute(cur, tile);
-            tile += gridDim.x;
-            if (tile >= nfull)
-                break;
-            tn = tile + gridDim.x < nfull ? tile + gridDim.x : tile;
-            lg_fwd16_load<IO, V, BLOCK, NT>(x, tn, cur);
-            compute(nxt, tile);
-            tile += gridDim.x;
-            if (tile >= nfull)
-                break;
-        }
-    }
+        });
     // the rest element by element: tiles from nfull on (all of them when not vec / not fast)
     for (; tile < ntiles; tile += gridDim.x)
         for (int64_t e = tile * kTile + threadIdx.x; e < (tile + 1) * kTile && e < n; e += BLOCK)
             y[e] = from_f32<IO>(lg_qdq(to_f32<IO>(x[e]), d, o, steps, rd));
 }
 
-// the element -> lane -> workgroup order of lg_bwd_tensor_kernel (tiles of kLgTile, 8 elements per
-// lane and step), so the sums equal the float32 kernel's on the upcast tensors
-template <int STEPS, bool NT>
-__device__ __forceinline__ void lg_bwd16_load(const unsigned short* __restrict__ x, const unsigned short* __restrict__ g,
-                                              int64_t base, u16x8* a, u16x8* b)
-{
-#pragma unroll
-    for (int u = 0; u < STEPS; ++u)
-    {
-        const int64_t q = lg_tile_elem(base, u, 0) / 8;
-        a[u] = ld16<NT>(reinterpret_cast<const u16x8*>(x) + q);
-        b[u] = ld16<NT>(reinterpret_cast<const u16x8*>(g) + q);
-    }
-}
-
-// Tiles b, b + grid, ... per workgroup with the next tile's loads issued before the current tile is
-// computed and reduced (see lg_fwd16_kernel); each tile's partial triple still goes to
-// partial[3 * tile], so the sums are those of any other grid.
-template <int IO, int STEPS, int MODE, bool NT = true>
+// lg_bwd_tensor_kernel's tiles and element -> lane -> workgroup order (lg_bwd_full_tile /
+// lg_bwd_elem_tile are its bodies too), so the sums equal the float32 kernel's on the upcast
+// tensors. The schedule differs: tiles b, b + grid, ... per workgroup with the next tile's loads
+// issued before the current tile is computed and reduced (lg_two_buffers; the kernel is VALU
+// co-bound, see lg_fwd16_kernel); each tile's partial triple still goes to partial[3 * tile], so
+// the sums are those of any other grid.
+template <int IO, int STEPS, int MODE>
 __global__ __launch_bounds__(kBlock) void lg_bwd16_tensor_kernel(const unsigned short* __restrict__ x,
                                                                  const unsigned short* __restrict__ g,
                                                                  unsigned short* __restrict__ gx, int64_t n,
@@ -964,81 +1017,25 @@ __global__ __launch_bounds__(kBlock) void lg_bwd16_tensor_kernel(const unsigned 
     // a small call (a few tiles per CU) the two latencies in a row were most of the kernel
     const int64_t nvec = vec ? n / kTile : 0;
     int64_t tile = blockIdx.x;
-    u16x8 a[STEPS], b[STEPS];
+    LgTileRegs<IO, STEPS> cur, nxt;
     if (tile < nvec)
-        lg_bwd16_load<STEPS, NT>(x, g, tile * kTile, a, b);
+        lg_bwd_load(x, g, tile * kTile, cur);
     const float dl = delta[0], o = offset[0], rcp = lg_recip(dl);
     // full tiles of an encoding lg_fast_enc accepts take the vector path; the rest (the partial
     // last tile, unaligned pointers, an encoding for the division) the element path
     const int64_t nfull = lg_fast_enc(o, rcp) ? nvec : 0;
-    // full tiles: two register buffers in turn, the next tile's loads unconditional (see
-    // lg_fwd16_kernel), each tile's partial triple published as before
-    auto full_tile = [&](const u16x8 (&a_)[STEPS], const u16x8 (&b_)[STEPS], int64_t t) {
-        const int64_t base = t * kTile;
-        Sums s {0, 0, 0};
-#pragma unroll
-        for (int u = 0; u < STEPS; ++u)
-        {
-            float r[8], xv[8], gv[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-            {
-                xv[k] = to_f32<IO>(a_[u][k]);
-                gv[k] = to_f32<IO>(b_[u][k]);
-            }
-            lg_bwd_elems_fast<8, MODE>(xv, gv, dl, o, steps, rcp, r, s);
-            if (gx)
-            {
-                u16x8 h;
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    h[k] = from_f32<IO>(r[k]);
-                st16<NT>(h, reinterpret_cast<u16x8*>(gx) + lg_tile_elem(base, u, 0) / 8);
-            }
-        }
-        Sums t3 = block_reduce(s);
-        if (threadIdx.x == 0)
-            store_sums(partial + 3 * t, t3);
-    };
-    if (tile < nfull)
-    {
-        u16x8 an[STEPS], bn[STEPS];
-        for (;;)
-        {
-            int64_t tn = tile + gridDim.x < nfull ? tile + gridDim.x : tile;
-            lg_bwd16_load<STEPS, NT>(x, g, tn * kTile, an, bn);
-            full_tile(a, b, tile);
-            tile += gridDim.x;
-            if (tile >= nfull)
-                break;
-            tn = tile + gridDim.x < nfull ? tile + gridDim.x : tile;
-            lg_bwd16_load<STEPS, NT>(x, g, tn * kTile, a, b);
-            full_tile(an, bn, tile);
-            tile += gridDim.x;
-            if (tile >= nfull)
-                break;
-        }
-    }
-    // the rest element by element (the partial last tile, unaligned pointers, an encoding for the
-    // division), the same order
+    tile = lg_two_buffers(
+        tile, nfull, cur, nxt, [&](int64_t t, LgTileRegs<IO, STEPS>& v) { lg_bwd_load(x, g, t * kTile, v); },
+        [&](const LgTileRegs<IO, STEPS>& v, int64_t t) {
+            Sums s {0, 0, 0};
+            lg_bwd_full_tile<IO, STEPS, MODE>(v, gx, t * kTile, dl, o, steps, rcp, s);
+            lg_publish(s, partial + 3 * t);
+        });
     for (; tile < ntiles; tile += gridDim.x)
     {
-        const int64_t base = tile * kTile;
         Sums s {0, 0, 0};
-        for (int u = 0; u < STEPS; ++u)
-            for (int k = 0; k < 8; ++k)
-            {
-                const int64_t e = lg_tile_elem(base, u, k);
-                if (e >= n)
-                    break;
-                float r;
-                lg_bwd_elem(to_f32<IO>(x[e]), to_f32<IO>(g[e]), dl, o, steps, rcp, r, s, MODE);
-                if (gx)
-                    gx[e] = from_f32<IO>(r);
-            }
-        Sums t3 = block_reduce(s);
-        if (threadIdx.x == 0)
-            store_sums(partial + 3 * tile, t3);
+        lg_bwd_elem_tile<IO, STEPS, MODE>(x, g, gx, tile * kTile, n, dl, o, steps, rcp, s);
+        lg_publish(s, partial + 3 * tile);
     }
 }
 
@@ -1090,38 +1087,29 @@ __global__ __launch_bounds__(kBlock) void lg_gate_many_kernel(LgGateSet set)
     emax[c] = t_maximum(mx, mn + 1e-5f);
 }
 
-// get_computed_encodings (quantsim_straight_through_grad.py:121-160)
-__global__ __launch_bounds__(kBlock) void lg_encodings_kernel(const float* __restrict__ emin,
-                                                              const float* __restrict__ emax, uint32_t C,
-                                                              float steps, int mode, float half_floor,
-                                                              float neg_half_ceil, float* __restrict__ delta,
-                                                              float* __restrict__ offset, float* __restrict__ range_out)
+// get_computed_encodings (quantsim_straight_through_grad.py:121-160) of every channel, on its own:
+// LgEnc::of and the stores the forward kernels make for the first element of each channel
+__global__ __launch_bounds__(kBlock) void lg_encodings_kernel(LgEnc enc)
 {
     const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
-    if (c >= C)
+    if (c >= enc.C)
         return;
-    const float mn = emin[c], mx = emax[c];
-    if (range_out)
+    const float mn = enc.emin[c], mx = enc.emax[c];
+    if (enc.range_out)
     {
-        range_out[c]     = mn;
-        range_out[C + c] = mx;
+        enc.range_out[c]         = mn;
+        enc.range_out[enc.C + c] = mx;
     }
     float d, o;
-    if (mode == 0)   // symmetric, signed
-    {
-        d = mx / half_floor;
-        o = neg_half_ceil;
-    }
-    else
-    {
-        d = (mx - mn) / steps;
-        if (mode == 1)   // symmetric, unsigned
-            o = mn / d;
-        else             // asymmetric: -min(steps, max(0, round(-min / delta)))
-            o = -t_minimum(steps, t_maximum(0.0f, __builtin_rintf(-mn / d)));
-    }
-    delta[c]  = d;
-    offset[c] = o;
+    enc.of(mn, mx, d, o);
+    enc.delta_out[c]  = d;
+    enc.offset_out[c] = o;
+}
+
+void launch_lg_encodings(const LgEnc& enc, hipStream_t s)
+{
+    lg_encodings_kernel<<<(unsigned) ceil_div(enc.C, kBlock), kBlock, 0, s>>>(enc);
+    AIMET_LAUNCH_CHECK();
 }
 
 // the encoding gradients from the backward's sums {A, B, D} (asymmetric / symmetric_gradients)
@@ -1154,20 +1142,123 @@ void launch_range_grads(const float* sums, int64_t C, const LgRange& r, hipStrea
     AIMET_LAUNCH_CHECK();
 }
 
-template <int GIO>
-void launch_bwd_tile(int U, int64_t wg, const f4* x, const void* g, f4* gx, FastDiv dk, FastDiv dc, int64_t C,
-                     const float* delta, const float* offset, float steps, int mode, float* partial, hipStream_t s)
+// f(integral_constant<IO_F16 or IO_BF16>) for a 16-bit dtype code the entry has checked
+template <class F>
+void with_io16(int dtype, F&& f)
 {
-    if (U == 4)
-        lg_bwd_tile_kernel<4, GIO><<<(unsigned) wg, kBlock, 0, s>>>(x, g, gx, dk, dc, (uint32_t) C, delta, offset,
-                                                                    steps, mode, partial);
-    else if (U == 2)
-        lg_bwd_tile_kernel<2, GIO><<<(unsigned) wg, kBlock, 0, s>>>(x, g, gx, dk, dc, (uint32_t) C, delta, offset,
-                                                                    steps, mode, partial);
+    if (dtype == IO_F16)
+        f(std::integral_constant<int, IO_F16> {});
     else
-        lg_bwd_tile_kernel<1, GIO><<<(unsigned) wg, kBlock, 0, s>>>(x, g, gx, dk, dc, (uint32_t) C, delta, offset,
-                                                                    steps, mode, partial);
+        f(std::integral_constant<int, IO_BF16> {});
+}
+
+// f(integral_constant<U>) for the tile form's quads per lane
+template <class F>
+void with_quads(int U, F&& f)
+{
+    switch (U)
+    {
+    case 4: f(std::integral_constant<int, 4> {}); break;
+    case 2: f(std::integral_constant<int, 2> {}); break;
+    default: f(std::integral_constant<int, 1> {}); break;
+    }
+}
+
+// What the three backward entries share once their own shape / dtype checks are done: the range
+// gradients' description, the mode (lg_bwd_term_m), the stream, and the pointer checks. An empty
+// tensor is finished here (zero sums and the range gradients of zero sums): `run` is then false.
+struct LgBackward
+{
+    LgRange range;
+    int mode;
+    hipStream_t s;
+    bool run;
+};
+
+LgBackward backward_begin(const void* x, const void* grad, const void* grad_x, float* sums, int64_t n, int64_t C,
+                          const float* delta, const float* offset, float num_steps,
+                          const aimet_lg_range_spec* range_spec, void* stream)
+{
+    LgBackward b {range_of(range_spec, num_steps), 0, as_stream(stream), n != 0};
+    b.mode = b.range.gmin == nullptr ? 0 : b.range.sym ? 1 : 2;
+    require_device_ptr(sums, "sums");
+    if (n == 0)
+    {
+        AIMET_HIP_CHECK(hipMemsetAsync(sums, 0, sizeof(float) * 3 * C, b.s));
+        launch_range_grads(sums, C, b.range, b.s);
+        return b;
+    }
+    require_device_ptr(x, "x");
+    require_device_ptr(grad, "grad");
+    if (grad_x)
+        require_device_ptr(grad_x, "grad_x");
+    require_device_ptr(delta, "delta");
+    require_device_ptr(offset, "offset");
+    return b;
+}
+
+// The tile form's conditions on a per-channel [outer][C][K] call: rows of whole workgroups
+// (K / 4 a multiple of 256), 32-bit quad indices, a fold of < 65536 channels, and 16-B aligned
+// float32 tensors. GRAD_ALIGN: the gradient's alignment, 16 B for a quad of floats, 8 B for a quad
+// of 16-bit values -- the only difference between the two callers.
+template <int GRAD_ALIGN>
+bool lg_tile_form(int64_t outer, int64_t C, int64_t K, const void* x, const void* grad, const void* grad_x)
+{
+    return K % 1024 == 0 && outer * C * K < (int64_t(1) << 31) && C < 65536 && aligned16(x, grad_x) &&
+           aligned_to<GRAD_ALIGN>(grad);
+}
+
+// per-channel, tile form (lg_tile_form holds): U quads per lane from the row length, one partial
+// triple per workgroup, folded per channel in a fixed order. GIO: the gradient's type; a 16-bit one
+// is upcast in the kernel's loads (exact), so the arithmetic and the summation order are those of
+// the float32 call on grad.to(float32).
+template <int GIO>
+void backward_tiles(const float* x, const void* grad, float* grad_x, float* sums, int64_t outer, int64_t C, int64_t K,
+                    const float* delta, const float* offset, float steps, const LgBackward& b)
+{
+    const int64_t K4 = K / 4;
+    const int U      = K4 % (kBlock * 4) == 0 ? 4 : K4 % (kBlock * 2) == 0 ? 2 : 1;
+    const int64_t wg = outer * C * K4 / (kBlock * U);
+    float* partial   = static_cast<float*>(scratch_alloc(sizeof(float) * 3 * wg, b.s));
+    with_quads(U, [&](auto u) {
+        lg_bwd_tile_kernel<decltype(u)::value, GIO><<<(unsigned) wg, kBlock, 0, b.s>>>(
+            reinterpret_cast<const f4*>(x), grad, reinterpret_cast<f4*>(grad_x), FastDiv((uint32_t) K4),
+            FastDiv((uint32_t) C), (uint32_t) C, delta, offset, steps, b.mode, partial);
+    });
     AIMET_LAUNCH_CHECK();
+    lg_bwd_tile_fold<<<(unsigned) ceil_div(C, kBlock), kBlock, 0, b.s>>>(
+        partial, sums, (uint32_t) outer, (uint32_t) C, (uint32_t) (K4 / (kBlock * U)), b.range);
+    AIMET_LAUNCH_CHECK();
+    scratch_free(partial, b.s);
+}
+
+// per-tensor: lg_bwd_launch's tiles, one partial triple per tile, folded by lg_bwd_fold_one. IO:
+// the type of x, grad and grad_x -- the float32 kernel (one tile per workgroup) or the 16-bit one
+// (pipelined); same tiles, same sums.
+template <int IO>
+void backward_tensor(const void* x, const void* grad, void* grad_x, float* sums, int64_t n, const float* delta,
+                     const float* offset, float steps, const LgBackward& b)
+{
+    typedef typename LgIo<IO>::elem_t T;
+    const int vec       = aligned16(x, grad, grad_x) ? 1 : 0;
+    const LgBwdLaunch L = lg_bwd_launch(n);
+    float* partial      = static_cast<float*>(scratch_alloc(sizeof(float) * 3 * L.ntiles, b.s));
+    auto xs = static_cast<const T*>(x);
+    auto gs = static_cast<const T*>(grad);
+    auto os = static_cast<T*>(grad_x);
+    lg_bwd_dispatch(b.mode, [&](auto md) {
+        constexpr int MD = decltype(md)::value;
+        if constexpr (IO == IO_F32)
+            lg_bwd_tensor_kernel<kLgTileSteps, MD><<<L.grid, kBlock, 0, b.s>>>(xs, gs, os, n, delta, offset, steps,
+                                                                               partial, vec, L.ntiles);
+        else
+            lg_bwd16_tensor_kernel<IO, kLgTileSteps, MD><<<L.grid16, kBlock, 0, b.s>>>(
+                xs, gs, os, n, delta, offset, steps, partial, vec, L.ntiles);
+    });
+    AIMET_LAUNCH_CHECK();
+    lg_bwd_fold_one<<<1, kBlock, 0, b.s>>>(partial, L.ntiles, sums, b.range);
+    AIMET_LAUNCH_CHECK();
+    scratch_free(partial, b.s);
 }
 
 }   // namespace
@@ -1266,10 +1357,7 @@ int aimet_lg_forward_range(const float* x, void* y, int64_t outer, int64_t C, in
         if (outer * C * K == 0)
         {
             // no element to carry the encodings: compute them on their own
-            lg_encodings_kernel<<<(unsigned) ceil_div(C, kBlock), kBlock, 0, as_stream(stream)>>>(
-                emin, emax, (uint32_t) C, enc.steps, enc.mode, enc.half_floor, enc.neg_half_ceil, delta_out,
-                offset_out, range_out);
-            AIMET_LAUNCH_CHECK();
+            launch_lg_encodings(enc, as_stream(stream));
             return;
         }
         forward_cast(x, y, outer, C, K, out_dtype, nullptr, nullptr, enc.steps, enc, as_stream(stream));
@@ -1311,10 +1399,7 @@ void forward_cast(const float* x, void* y, int64_t outer, int64_t C, int64_t K, 
             // (or channel ranges, or row pieces) of <= lg_chunk_elems() elements each
             if (enc.emin)
             {
-                lg_encodings_kernel<<<(unsigned) ceil_div(C, kBlock), kBlock, 0, st>>>(
-                    enc.emin, enc.emax, (uint32_t) C, enc.steps, enc.mode, enc.half_floor, enc.neg_half_ceil,
-                    enc.delta_out, enc.offset_out, enc.range_out);
-                AIMET_LAUNCH_CHECK();
+                launch_lg_encodings(enc, st);
                 delta  = enc.delta_out;
                 offset = enc.offset_out;
             }
@@ -1325,16 +1410,16 @@ void forward_cast(const float* x, void* y, int64_t outer, int64_t C, int64_t K, 
             });
             return;
         }
-        LgChannel map {FastDiv((uint32_t) (K > 0 ? K : 1)), FastDiv((uint32_t) C), (uint32_t) C};
-        const int ya = out_dtype == IO_F32 ? 15 : 7;
-        bool vec = (C == 1 || K % 4 == 0) && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(y) & ya) == 0 && n % 4 == 0;
+        const LgChannel map(C, K);
+        // a quad of y is 16 B of floats or 8 B of 16-bit values
+        const bool y_aligned = out_dtype == IO_F32 ? aligned16(y) : aligned_to<8>(y);
+        const bool vec       = (C == 1 || K % 4 == 0) && aligned16(x) && y_aligned && n % 4 == 0;
         if (out_dtype == IO_F32)
             launch_lg_fwd<IO_F32>(x, y, n, map, delta, offset, num_steps, vec, enc, st);
-        else if (out_dtype == IO_F16)
-            launch_lg_fwd<IO_F16>(x, y, n, map, delta, offset, num_steps, vec, enc, st);
         else
-            launch_lg_fwd<IO_BF16>(x, y, n, map, delta, offset, num_steps, vec, enc, st);
+            with_io16(out_dtype, [&](auto io) {
+                launch_lg_fwd<decltype(io)::value>(x, y, n, map, delta, offset, num_steps, vec, enc, st);
+            });
     }
 }
 
@@ -1348,63 +1433,16 @@ int aimet_lg_backward(const float* x, const float* grad, float* grad_x, float* s
 {
     return guarded([&] {
         AIMET_REQUIRE(outer >= 0 && C > 0 && K >= 0, "invalid shape");
-        int64_t n = outer * C * K;
-        require_device_ptr(sums, "sums");
-        hipStream_t s = as_stream(stream);
-        const LgRange range = range_of(range_spec, num_steps);
-        const int mode      = range.gmin == nullptr ? 0 : range.sym ? 1 : 2;   // lg_bwd_term_m
-        if (n == 0)
-        {
-            AIMET_HIP_CHECK(hipMemsetAsync(sums, 0, sizeof(float) * 3 * C, s));
-            launch_range_grads(sums, C, range, s);
+        const int64_t n = outer * C * K;
+        const LgBackward b =
+            backward_begin(x, grad, grad_x, sums, n, C, delta, offset, num_steps, range_spec, stream);
+        if (!b.run)
             return;
-        }
-        require_device_ptr(x, "x");
-        require_device_ptr(grad, "grad");
-        if (grad_x)
-            require_device_ptr(grad_x, "grad_x");
-        require_device_ptr(delta, "delta");
-        require_device_ptr(offset, "offset");
         if (C == 1)
-        {
-            bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad) |
-                         reinterpret_cast<uintptr_t>(grad_x)) & 15) == 0;
-            const LgBwdLaunch L = lg_bwd_launch(n);
-            float* partial      = static_cast<float*>(scratch_alloc(sizeof(float) * 3 * L.ntiles, s));
-            const int v         = vec ? 1 : 0;
-            lg_bwd_dispatch(mode, [&](auto md) {
-                lg_bwd_tensor_kernel<kLgTileSteps, decltype(md)::value><<<L.grid, kBlock, 0, s>>>(
-                    x, grad, grad_x, n, delta, offset, num_steps, partial, v, L.ntiles);
-            });
-            AIMET_LAUNCH_CHECK();
-            lg_bwd_fold_one<<<1, kBlock, 0, s>>>(partial, L.ntiles, sums, range);
-            AIMET_LAUNCH_CHECK();
-            scratch_free(partial, s);
-            return;
-        }
-        else if (K % 1024 == 0 && n < (int64_t(1) << 31) && C < 65536 &&
-                 ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad) |
-                   reinterpret_cast<uintptr_t>(grad_x)) & 15) == 0)
-        {
-            const int64_t K4 = K / 4;
-            const int U      = K4 % (kBlock * 4) == 0 ? 4 : K4 % (kBlock * 2) == 0 ? 2 : 1;
-            const int64_t wg = n / 4 / (kBlock * U);
-            float* partial   = nullptr;
-            partial = static_cast<float*>(scratch_alloc(sizeof(float) * 3 * wg, s));
-            auto xv = reinterpret_cast<const f4*>(x);
-            auto gv = reinterpret_cast<const f4*>(grad);
-            auto ov = reinterpret_cast<f4*>(grad_x);
-            FastDiv dk((uint32_t) K4), dc((uint32_t) C);
-            launch_bwd_tile<IO_F32>(U, wg, xv, gv, ov, dk, dc, C, delta, offset, num_steps, mode, partial, s);
-            lg_bwd_tile_fold<<<(unsigned) ceil_div(C, kBlock), kBlock, 0, s>>>(
-                partial, sums, (uint32_t) outer, (uint32_t) C, (uint32_t) (K4 / (kBlock * U)), range);
-            AIMET_LAUNCH_CHECK();
-            scratch_free(partial, s);
-            return;
-        }
-        else if (K % 4 == 0 && outer * (K / 4) < (int64_t(1) << 32) &&
-                 ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad) |
-                   reinterpret_cast<uintptr_t>(grad_x)) & 15) == 0)
+            return backward_tensor<IO_F32>(x, grad, grad_x, sums, n, delta, offset, num_steps, b);
+        if (lg_tile_form<16>(outer, C, K, x, grad, grad_x))
+            return backward_tiles<IO_F32>(x, grad, grad_x, sums, outer, C, K, delta, offset, num_steps, b);
+        if (K % 4 == 0 && outer * (K / 4) < (int64_t(1) << 32) && aligned16(x, grad, grad_x))
         {
             // >= 2048 workgroups in flight: slice channels when there are fewer than that
             const int64_t K4  = K / 4;
@@ -1413,29 +1451,29 @@ int aimet_lg_backward(const float* x, const float* grad, float* grad_x, float* s
             if (splits > per)
                 splits = per > 0 ? per : 1;
             dim3 grid((unsigned) (C < 65536 ? C : 65536), (unsigned) splits);
-            float* partial = splits > 1 ? static_cast<float*>(scratch_alloc(sizeof(float) * 3 * C * splits, s))
+            float* partial = splits > 1 ? static_cast<float*>(scratch_alloc(sizeof(float) * 3 * C * splits, b.s))
                                         : sums;
-            lg_bwd_channel_vec_kernel<<<grid, kBlock, 0, s>>>(
+            lg_bwd_channel_vec_kernel<<<grid, kBlock, 0, b.s>>>(
                 reinterpret_cast<const f4*>(x), reinterpret_cast<const f4*>(grad), reinterpret_cast<f4*>(grad_x),
-                outer, C, K4, FastDiv((uint32_t) (K4 > 0 ? K4 : 1)), delta, offset, num_steps, mode, partial);
+                outer, C, K4, FastDiv((uint32_t) (K4 > 0 ? K4 : 1)), delta, offset, num_steps, b.mode, partial);
             if (splits > 1)
             {
                 AIMET_LAUNCH_CHECK();
-                lg_bwd_tile_fold<<<(unsigned) ceil_div(C, kBlock), kBlock, 0, s>>>(partial, sums, 1u, (uint32_t) C,
-                                                                                   (uint32_t) splits, range);
+                lg_bwd_tile_fold<<<(unsigned) ceil_div(C, kBlock), kBlock, 0, b.s>>>(partial, sums, 1u, (uint32_t) C,
+                                                                                   (uint32_t) splits, b.range);
                 AIMET_LAUNCH_CHECK();
-                scratch_free(partial, s);
+                scratch_free(partial, b.s);
                 return;
             }
         }
         else
         {
             int grid = (int) (C < 65536 ? C : 65536);
-            lg_bwd_channel_kernel<<<grid, kBlock, 0, s>>>(x, grad, grad_x, outer, C, K, delta, offset, num_steps,
-                                                          mode, sums);
+            lg_bwd_channel_kernel<<<grid, kBlock, 0, b.s>>>(x, grad, grad_x, outer, C, K, delta, offset, num_steps,
+                                                          b.mode, sums);
         }
         AIMET_LAUNCH_CHECK();
-        launch_range_grads(sums, C, range, s);
+        launch_range_grads(sums, C, b.range, b.s);
     });
 }
 
@@ -1453,19 +1491,16 @@ void forward_16(const void* x, void* y, int64_t n, int io_dtype, const float* de
         return;
     require_device_ptr(x, "x");
     require_device_ptr(y, "y");
-    const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+    const int v = aligned16(x, y) ? 1 : 0;
     auto xs = static_cast<const unsigned short*>(x);
     auto ys = static_cast<unsigned short*>(y);
     // kLgFwd16Vecs 16-B vectors per lane, kLgFwd16Grid workgroups looping over the tiles
     const int64_t ntiles = ceil_div(n, kLgFwd16Tile);
     const unsigned grid  = (unsigned) (ntiles > kLgFwd16Grid ? kLgFwd16Grid : ntiles);
-    const int v          = vec ? 1 : 0;
-    if (io_dtype == IO_F16)
-        lg_fwd16_kernel<IO_F16, kLgFwd16Vecs, kBlock><<<grid, kBlock, 0, st>>>(xs, ys, n, delta, offset, num_steps, v,
-                                                                              enc, ntiles);
-    else
-        lg_fwd16_kernel<IO_BF16, kLgFwd16Vecs, kBlock><<<grid, kBlock, 0, st>>>(xs, ys, n, delta, offset, num_steps, v,
-                                                                               enc, ntiles);
+    with_io16(io_dtype, [&](auto io) {
+        lg_fwd16_kernel<decltype(io)::value, kLgFwd16Vecs, kBlock><<<grid, kBlock, 0, st>>>(
+            xs, ys, n, delta, offset, num_steps, v, enc, ntiles);
+    });
     AIMET_LAUNCH_CHECK();
 }
 
@@ -1492,10 +1527,7 @@ int aimet_lg_forward_16_range(const void* x, void* y, int64_t n, int io_dtype, c
                                  range_out);
         if (n == 0)
         {
-            lg_encodings_kernel<<<1, kBlock, 0, as_stream(stream)>>>(emin, emax, 1u, enc.steps, enc.mode,
-                                                                      enc.half_floor, enc.neg_half_ceil, delta_out,
-                                                                      offset_out, range_out);
-            AIMET_LAUNCH_CHECK();
+            launch_lg_encodings(enc, as_stream(stream));
             return;
         }
         forward_16(x, y, n, io_dtype, nullptr, nullptr, enc.steps, enc, as_stream(stream));
@@ -1557,15 +1589,8 @@ int aimet_lg_encodings(const float* emin, const float* emax, int64_t C, int bw, 
         AIMET_REQUIRE(bw > 0 && bw < 32, "invalid bitwidth");
         if (C == 0)
             return;
-        double steps = std::ldexp(1.0, bw) - 1;
-        if (sym && strict)
-            steps -= 1;
-        const double half = steps / 2;
-        const int mode    = (sym && !unsign) ? 0 : (sym ? 1 : 2);
-        lg_encodings_kernel<<<(unsigned) ceil_div(C, kBlock), kBlock, 0, as_stream(stream)>>>(
-            emin, emax, (uint32_t) C, (float) steps, mode, (float) std::floor(half), (float) -std::ceil(half), delta,
-            offset, nullptr);
-        AIMET_LAUNCH_CHECK();
+        launch_lg_encodings(enc_of(emin, emax, C, 1, bw, sym, strict, unsign, delta, offset, nullptr),
+                            as_stream(stream));
     });
 }
 
@@ -1584,54 +1609,24 @@ int aimet_lg_backward_grad16(const float* x, const void* grad, float* grad_x, fl
                              const aimet_lg_range_spec* range_spec, void* stream)
 {
     return guarded([&] {
-        const LgRange range = range_of(range_spec, num_steps);
-        const int mode      = range.gmin == nullptr ? 0 : range.sym ? 1 : 2;   // lg_bwd_term_m
         AIMET_REQUIRE(grad_dtype == IO_F16 || grad_dtype == IO_BF16, "grad_dtype must be 1 (float16) or 2 (bfloat16)");
         AIMET_REQUIRE(outer >= 0 && C > 1 && K >= 0, "invalid shape (per-channel tensors only)");
-        const int64_t n = outer * C * K;
-        require_device_ptr(sums, "sums");
-        hipStream_t s = as_stream(stream);
-        if (n == 0)
-        {
-            AIMET_HIP_CHECK(hipMemsetAsync(sums, 0, sizeof(float) * 3 * C, s));
-            launch_range_grads(sums, C, range, s);
-            return;
-        }
-        AIMET_REQUIRE(aimet_lg_backward_grad16_supported(outer, C, K, x, grad, grad_x),
+        AIMET_REQUIRE(outer * C * K == 0 || aimet_lg_backward_grad16_supported(outer, C, K, x, grad, grad_x),
                       "16-bit gradient backward: rows must be multiples of 1024 elements, 16-B / 8-B aligned");
-        require_device_ptr(x, "x");
-        require_device_ptr(grad, "grad");
-        if (grad_x)
-            require_device_ptr(grad_x, "grad_x");
-        require_device_ptr(delta, "delta");
-        require_device_ptr(offset, "offset");
-        // the tile path of aimet_lg_backward with the gradient upcast in registers (exact): the same
-        // arithmetic and summation order as aimet_lg_backward on grad.to(float32)
-        const int64_t K4 = K / 4;
-        const int U      = K4 % (kBlock * 4) == 0 ? 4 : K4 % (kBlock * 2) == 0 ? 2 : 1;
-        const int64_t wg = n / 4 / (kBlock * U);
-        float* partial   = static_cast<float*>(scratch_alloc(sizeof(float) * 3 * wg, s));
-        FastDiv dk((uint32_t) K4), dc((uint32_t) C);
-        auto xv = reinterpret_cast<const f4*>(x);
-        auto ov = reinterpret_cast<f4*>(grad_x);
-        if (grad_dtype == IO_F16)
-            launch_bwd_tile<IO_F16>(U, wg, xv, grad, ov, dk, dc, C, delta, offset, num_steps, mode, partial, s);
-        else
-            launch_bwd_tile<IO_BF16>(U, wg, xv, grad, ov, dk, dc, C, delta, offset, num_steps, mode, partial, s);
-        lg_bwd_tile_fold<<<(unsigned) ceil_div(C, kBlock), kBlock, 0, s>>>(
-            partial, sums, (uint32_t) outer, (uint32_t) C, (uint32_t) (K4 / (kBlock * U)), range);
-        AIMET_LAUNCH_CHECK();
-        scratch_free(partial, s);
+        const LgBackward b =
+            backward_begin(x, grad, grad_x, sums, outer * C * K, C, delta, offset, num_steps, range_spec, stream);
+        if (!b.run)
+            return;
+        with_io16(grad_dtype, [&](auto gio) {
+            backward_tiles<decltype(gio)::value>(x, grad, grad_x, sums, outer, C, K, delta, offset, num_steps, b);
+        });
     });
 }
 
 int aimet_lg_backward_grad16_supported(int64_t outer, int64_t C, int64_t K, const void* x, const void* grad,
                                        const void* grad_x)
 {
-    const int64_t n = outer * C * K;
-    return C > 1 && K % 1024 == 0 && n > 0 && n < (int64_t(1) << 31) && C < 65536 &&
-           ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad_x)) & 15) == 0 &&
-           (reinterpret_cast<uintptr_t>(grad) & 7) == 0;
+    return C > 1 && outer * C * K > 0 && lg_tile_form<8>(outer, C, K, x, grad, grad_x);
 }
 
 int aimet_lg_backward_16(const void* x, const void* grad, void* grad_x, float* sums, int64_t n, int io_dtype,
@@ -1639,45 +1634,14 @@ int aimet_lg_backward_16(const void* x, const void* grad, void* grad_x, float* s
                          const aimet_lg_range_spec* range_spec, void* stream)
 {
     return guarded([&] {
-        const LgRange range = range_of(range_spec, num_steps);
-        const int mode      = range.gmin == nullptr ? 0 : range.sym ? 1 : 2;   // lg_bwd_term_m
         AIMET_REQUIRE(io_dtype == IO_F16 || io_dtype == IO_BF16, "io_dtype must be 1 (float16) or 2 (bfloat16)");
         AIMET_REQUIRE(n >= 0, "invalid size");
-        require_device_ptr(sums, "sums");
-        hipStream_t s = as_stream(stream);
-        if (n == 0)
-        {
-            AIMET_HIP_CHECK(hipMemsetAsync(sums, 0, sizeof(float) * 3, s));
-            launch_range_grads(sums, 1, range, s);
+        const LgBackward b = backward_begin(x, grad, grad_x, sums, n, 1, delta, offset, num_steps, range_spec, stream);
+        if (!b.run)
             return;
-        }
-        require_device_ptr(x, "x");
-        require_device_ptr(grad, "grad");
-        if (grad_x)
-            require_device_ptr(grad_x, "grad_x");
-        require_device_ptr(delta, "delta");
-        require_device_ptr(offset, "offset");
-        const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad) |
-                           reinterpret_cast<uintptr_t>(grad_x)) & 15) == 0;
-        const LgBwdLaunch L = lg_bwd_launch(n);   // the fp32 kernel's tiles
-        float* partial      = static_cast<float*>(scratch_alloc(sizeof(float) * 3 * L.ntiles, s));
-        auto xs = static_cast<const unsigned short*>(x);
-        auto gs = static_cast<const unsigned short*>(grad);
-        auto os = static_cast<unsigned short*>(grad_x);
-        const int v = vec ? 1 : 0;
-        lg_bwd_dispatch(mode, [&](auto md) {
-            constexpr int MD = decltype(md)::value;
-            if (io_dtype == IO_F16)
-                lg_bwd16_tensor_kernel<IO_F16, kLgTileSteps, MD><<<L.grid16, kBlock, 0, s>>>(
-                    xs, gs, os, n, delta, offset, num_steps, partial, v, L.ntiles);
-            else
-                lg_bwd16_tensor_kernel<IO_BF16, kLgTileSteps, MD><<<L.grid16, kBlock, 0, s>>>(
-                    xs, gs, os, n, delta, offset, num_steps, partial, v, L.ntiles);
+        with_io16(io_dtype, [&](auto io) {
+            backward_tensor<decltype(io)::value>(x, grad, grad_x, sums, n, delta, offset, num_steps, b);
         });
-        AIMET_LAUNCH_CHECK();
-        lg_bwd_fold_one<<<1, kBlock, 0, s>>>(partial, L.ntiles, sums, range);
-        AIMET_LAUNCH_CHECK();
-        scratch_free(partial, s);
     });
 }
 

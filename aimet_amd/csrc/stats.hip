@@ -33,7 +33,6 @@ namespace
 constexpr int kWaves      = kBlock / 64;
 constexpr int kHistUnroll = 4;
 constexpr int kHistGrid   = 2048;   // 8 workgroups per CU: enough 16-B loads in flight for HBM
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float wave_min(float v)
 {

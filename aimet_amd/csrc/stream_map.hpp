@@ -25,8 +25,6 @@
 namespace aimet_amd
 {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 // streamed once: kept out of L2 / MALL
 template <class V>
 __device__ __forceinline__ V load_stream(const V* p)
@@ -49,10 +47,16 @@ __device__ __forceinline__ void independent_of(const float* out, const P*... in)
     (__builtin_assume_separate_storage(out, in), ...);
 }
 
+// every pointer a multiple of A bytes (a null pointer is)
+template <int A, class... P>
+inline bool aligned_to(const P*... p)
+{
+    return ((reinterpret_cast<uintptr_t>(p) | ...) & (A - 1)) == 0;
+}
 template <class... P>
 inline bool aligned16(const P*... p)
 {
-    return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
+    return aligned_to<16>(p...);
 }
 
 // channel of element i of [outer][C][K] (i < 2^31)

@@ -126,80 +126,55 @@ class LearnedGridQuantizeDequantize(torch.autograd.Function):
                 is_unsigned_symmetric=False, ch_axis=0, out_dtype=None):
         if bitwidth >= 32:
             raise RuntimeError("Invalid bitwidth: %d" % bitwidth)
+        flags = (bitwidth, use_symmetric, use_strict_symmetric, is_unsigned_symmetric)
         orig_dtype = tensor.dtype
         if out_dtype in IO_DTYPES and orig_dtype == torch.float32 and tensor.is_cuda and encoding_min.numel() > 1:
-            return LearnedGridQuantizeDequantize._forward_cast(ctx, tensor, encoding_min, encoding_max, bitwidth,
-                                                               use_symmetric, use_strict_symmetric,
-                                                               is_unsigned_symmetric, ch_axis, out_dtype)
+            # float32 per-channel tensor, 16-bit result (the cast in the kernel's store); saves the
+            # float32 input
+            return LearnedGridQuantizeDequantize._run(ctx, tensor, encoding_min, encoding_max, flags, ch_axis,
+                                                      torch.float32, out_dtype)
         if tensor.is_cuda and orig_dtype in IO_DTYPES and encoding_min.numel() == 1:
-            return LearnedGridQuantizeDequantize._forward_16(ctx, tensor, encoding_min, encoding_max, bitwidth,
-                                                             use_symmetric, use_strict_symmetric,
-                                                             is_unsigned_symmetric)
+            # fp16 / bf16 tensor, per-tensor range: aimet_lg_forward_16 (the casts in registers;
+            # identical to the upcast -> fp32 kernel -> downcast chain); saves the 16-bit input
+            return LearnedGridQuantizeDequantize._run(ctx, tensor, encoding_min, encoding_max, flags, ch_axis,
+                                                      orig_dtype, orig_dtype)
         # a CPU tensor (and its CPU range) is staged through HBM; results go back to the host
         x, staged = _stage(tensor.to(torch.float32), "tensor")
-        x = x.contiguous()
-        emin = encoding_min.detach().to(x.device, torch.float32).reshape(-1).contiguous()
-        emax = encoding_max.detach().to(x.device, torch.float32).reshape(-1).contiguous()
-        outer, C, K = _channels(x.shape, ch_axis, emin.numel() > 1)
-        if C != emin.numel():
-            raise ValueError("encoding has %d channels, tensor has %d along axis %d" % (emin.numel(), C, ch_axis))
-        y = torch.empty_like(x)
-        # get_computed_encodings inside the forward kernel (delta / offset stored for the backward,
-        # with a copy of the range as the kernel read it)
-        enc = _saved_encoding(emin)
-        steps = num_steps_of(bitwidth, use_symmetric, use_strict_symmetric)
-        with torch.cuda.device(x.device):
-            _native.call("aimet_lg_forward_range", x.data_ptr(), y.data_ptr(), outer, C, K, 0, emin.data_ptr(),
-                         emax.data_ptr(), int(bitwidth), int(bool(use_symmetric)), int(bool(use_strict_symmetric)),
-                         int(bool(is_unsigned_symmetric)), enc[0].data_ptr(), enc[1].data_ptr(), enc[2].data_ptr(),
-                         _stream(x))
-        ctx.save_for_backward(x, enc)
-        ctx.cfg = (outer, C, K, steps, use_symmetric, is_unsigned_symmetric, orig_dtype,
-                   encoding_min.shape, encoding_max.shape, staged)
+        y = LearnedGridQuantizeDequantize._run(ctx, x, encoding_min, encoding_max, flags, ch_axis, orig_dtype,
+                                               torch.float32, staged)
         return y.to(orig_dtype).cpu() if staged else y.to(orig_dtype)
 
     @staticmethod
-    def _forward_cast(ctx, tensor, encoding_min, encoding_max, bitwidth, use_symmetric, use_strict_symmetric,
-                      is_unsigned_symmetric, ch_axis, out_dtype):
-        """float32 per-channel tensor, 16-bit result (aimet_lg_forward_cast). Saves the float32 input."""
-        x = tensor.contiguous()
+    def _run(ctx, x, encoding_min, encoding_max, flags, ch_axis, grad_dtype, y_dtype, staged=False):
+        """The forward every variant shares: the range as contiguous float32 device vectors, one
+        native call that computes the encodings in the kernel (get_computed_encodings; delta /
+        offset stored for the backward with a copy of the range as the kernel read it), and the
+        state the backward needs. x: float32 (y_dtype float32, or fp16 / bf16 for the fused cast) or,
+        with a per-tensor range, 16-bit (y_dtype == x.dtype). grad_dtype: what grad_x is cast to."""
+        bitwidth, use_symmetric, use_strict_symmetric, is_unsigned_symmetric = flags
+        x = x.contiguous()
         emin = encoding_min.detach().to(x.device, torch.float32).reshape(-1).contiguous()
         emax = encoding_max.detach().to(x.device, torch.float32).reshape(-1).contiguous()
-        outer, C, K = _channels(x.shape, ch_axis, True)
-        if C != emin.numel():
-            raise ValueError("encoding has %d channels, tensor has %d along axis %d" % (emin.numel(), C, ch_axis))
-        y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+        if x.dtype in IO_DTYPES:
+            outer, C, K = 1, 1, x.numel()
+        else:
+            outer, C, K = _channels(x.shape, ch_axis, emin.numel() > 1)
+            if C != emin.numel():
+                raise ValueError("encoding has %d channels, tensor has %d along axis %d" % (emin.numel(), C, ch_axis))
+        y = torch.empty(x.shape, dtype=y_dtype, device=x.device)
         enc = _saved_encoding(emin)
-        steps = num_steps_of(bitwidth, use_symmetric, use_strict_symmetric)
+        grid = (emin.data_ptr(), emax.data_ptr(), int(bitwidth), int(bool(use_symmetric)),
+                int(bool(use_strict_symmetric)), int(bool(is_unsigned_symmetric)), enc[0].data_ptr(),
+                enc[1].data_ptr(), enc[2].data_ptr(), _stream(x))
         with torch.cuda.device(x.device):
-            _native.call("aimet_lg_forward_range", x.data_ptr(), y.data_ptr(), outer, C, K, IO_DTYPES[out_dtype],
-                         emin.data_ptr(), emax.data_ptr(), int(bitwidth), int(bool(use_symmetric)),
-                         int(bool(use_strict_symmetric)), int(bool(is_unsigned_symmetric)), enc[0].data_ptr(),
-                         enc[1].data_ptr(), enc[2].data_ptr(), _stream(x))
+            if x.dtype in IO_DTYPES:
+                _native.call("aimet_lg_forward_16_range", x.data_ptr(), y.data_ptr(), K, IO_DTYPES[x.dtype], *grid)
+            else:
+                _native.call("aimet_lg_forward_range", x.data_ptr(), y.data_ptr(), outer, C, K,
+                             IO_DTYPES.get(y_dtype, 0), *grid)
         ctx.save_for_backward(x, enc)
-        ctx.cfg = (outer, C, K, steps, use_symmetric, is_unsigned_symmetric, torch.float32,
-                   encoding_min.shape, encoding_max.shape, False)
-        return y
-
-    @staticmethod
-    def _forward_16(ctx, tensor, encoding_min, encoding_max, bitwidth, use_symmetric, use_strict_symmetric,
-                    is_unsigned_symmetric):
-        """fp16 / bf16 tensor, per-tensor range: aimet_lg_forward_16 (the casts in registers;
-        identical to the upcast -> fp32 kernel -> downcast chain). Saves the 16-bit input."""
-        x = tensor.contiguous()
-        emin = encoding_min.detach().to(x.device, torch.float32).reshape(-1).contiguous()
-        emax = encoding_max.detach().to(x.device, torch.float32).reshape(-1).contiguous()
-        y = torch.empty_like(x)
-        enc = _saved_encoding(emin)
-        steps = num_steps_of(bitwidth, use_symmetric, use_strict_symmetric)
-        with torch.cuda.device(x.device):
-            _native.call("aimet_lg_forward_16_range", x.data_ptr(), y.data_ptr(), x.numel(), IO_DTYPES[x.dtype],
-                         emin.data_ptr(), emax.data_ptr(), int(bitwidth), int(bool(use_symmetric)),
-                         int(bool(use_strict_symmetric)), int(bool(is_unsigned_symmetric)), enc[0].data_ptr(),
-                         enc[1].data_ptr(), enc[2].data_ptr(), _stream(x))
-        ctx.save_for_backward(x, enc)
-        ctx.cfg = (1, 1, x.numel(), steps, use_symmetric, is_unsigned_symmetric, x.dtype,
-                   encoding_min.shape, encoding_max.shape, False)
+        ctx.cfg = (outer, C, K, num_steps_of(bitwidth, use_symmetric, use_strict_symmetric), use_symmetric,
+                   is_unsigned_symmetric, grad_dtype, encoding_min.shape, encoding_max.shape, staged)
         return y
 
     @staticmethod
@@ -216,31 +191,28 @@ class LearnedGridQuantizeDequantize(torch.autograd.Function):
         gmax = torch.empty_like(emax)
         spec = ctypes.byref(_RangeSpec(emin.data_ptr(), emax.data_ptr(), delta.data_ptr(), gmin.data_ptr(),
                                        gmax.data_ptr(), int(bool(sym))))
+        want_gx = ctx.needs_input_grad[0]
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
         g16 = grad.contiguous() if (x.dtype == torch.float32 and grad.dtype in IO_DTYPES and grad.is_cuda
                                     and C > 1) else None
-        gx = torch.empty_like(x) if (g16 is not None and ctx.needs_input_grad[0]) else None
+        gx = torch.empty_like(x) if (g16 is not None and want_gx) else None
         if g16 is not None and _native.load().aimet_lg_backward_grad16_supported(
-                outer, C, K, x.data_ptr(), g16.data_ptr(), gx.data_ptr() if gx is not None else None):
+                outer, C, K, x.data_ptr(), g16.data_ptr(), ptr(gx)):
             # the 16-bit weight gradient of a cast-fused forward, upcast in the kernel's loads
-            with torch.cuda.device(x.device):
-                _native.call("aimet_lg_backward_grad16", x.data_ptr(), g16.data_ptr(),
-                             gx.data_ptr() if gx is not None else None, sums.data_ptr(), outer, C, K,
-                             IO_DTYPES[g16.dtype], delta.data_ptr(), offset.data_ptr(), steps, spec, _stream(x))
+            name, g, shape = "aimet_lg_backward_grad16", g16, (outer, C, K, IO_DTYPES[g16.dtype])
         elif x.dtype in IO_DTYPES and grad.dtype == x.dtype and grad.is_cuda:
-            g = grad.contiguous()
-            gx = torch.empty_like(g) if ctx.needs_input_grad[0] else None
-            with torch.cuda.device(x.device):
-                _native.call("aimet_lg_backward_16", x.data_ptr(), g.data_ptr(),
-                             gx.data_ptr() if gx is not None else None, sums.data_ptr(), x.numel(), IO_DTYPES[x.dtype],
-                             delta.data_ptr(), offset.data_ptr(), steps, spec, _stream(x))
+            name, g, shape = "aimet_lg_backward_16", grad.contiguous(), (x.numel(), IO_DTYPES[x.dtype])
         else:
             x = x.to(torch.float32)   # a 16-bit input with a gradient of another dtype
-            g = grad.to(x.device, torch.float32).contiguous()
-            gx = torch.empty_like(g) if ctx.needs_input_grad[0] else None
-            with torch.cuda.device(x.device):
-                _native.call("aimet_lg_backward", x.data_ptr(), g.data_ptr(), gx.data_ptr() if gx is not None else None,
-                             sums.data_ptr(), outer, C, K, delta.data_ptr(), offset.data_ptr(), steps, spec,
-                             _stream(x))
+            name, g, shape = "aimet_lg_backward", grad.to(x.device, torch.float32).contiguous(), (outer, C, K)
+        if g is not g16:
+            gx = torch.empty_like(g) if want_gx else None
+        with torch.cuda.device(x.device):
+            _native.call(name, x.data_ptr(), g.data_ptr(), ptr(gx), sums.data_ptr(), *shape, delta.data_ptr(),
+                         offset.data_ptr(), steps, spec, _stream(x))
         gx_out = gx.to(dtype) if gx is not None else None
         gmin, gmax = gmin.view(min_shape), gmax.view(max_shape)
         if staged:

@@ -726,12 +726,15 @@ def test_learned_grid_non_finite_inputs_follow_torch(sym):
         assert torch.equal(yh.view(torch.int16), want.view(torch.int16)), dt
 
 
-@pytest.mark.parametrize("outer,C,K", [(3, 5, 2048), (2, 7, 3072), (4, 3, 100)])
+@pytest.mark.parametrize("outer,C,K", [(3, 5, 2048), (2, 7, 3072), (4, 3, 100), (1, 2048, 12), (2, 5, 1028),
+                                       (1, 3, 4096)])
 def test_learned_grid_backward_sums_channel_axis_inner(outer, C, K):
     """aimet_lg_backward on [outer][C][K] with outer > 1 (channel axis not first): grad_x exact and
     the per-channel sums A = sum((x_q + o) g), B = sum(mask x/delta g), D = sum(!mask g) against
     float64 numpy (rtol 1e-4: fp32 accumulation order). Covers the tile form (K % 1024 == 0, 4 and 2
-    quads per lane) and the channel form."""
+    quads per lane; (1, 3, 4096): 4 quads, one workgroup per row), the channel form, and the
+    16-B channel x slice form with one slice per channel (1, 2048, 12) and with several slices over
+    outer > 1 (2, 5, 1028)."""
     from aimet_amd import _native
     g0 = torch.Generator(device=DEV).manual_seed(outer * 100 + C)
     x = torch.randn(outer, C, K, device=DEV, generator=g0) * 0.3
@@ -1102,11 +1105,12 @@ def test_recon_loss_backward_fused_vs_torch(act, shape):
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("sym", [True, False])
-@pytest.mark.parametrize("K", [4096, 1000])
+@pytest.mark.parametrize("K", [4096, 1000, 1024, 2048])
 def test_learned_grid_cast_fused_weight_equals_cast_after(dtype, sym, K):
     """out_dtype: aimet_lg_forward_cast == the float32 op then .to(dtype); aimet_lg_backward_grad16
     on the 16-bit gradient == the float32 backward on grad.to(float32) -- y, grad_x and both range
-    gradients bit for bit (per-channel [C, K] weights with K a multiple of 1024)."""
+    gradients bit for bit (per-channel [C, K] weights with K a multiple of 1024: 4096, 2048 and 1024
+    take the tile kernel with 4, 2 and 1 quads per lane)."""
     from aimet_amd.learned_grid import LearnedGridQuantizeDequantize as LG
     g = torch.Generator(device=DEV).manual_seed(41 + int(sym))
     C = 96   # K = 1000: rows not a multiple of 1024 -> the backward upcasts the gradient first
@@ -1336,6 +1340,93 @@ def test_learned_grid_16bit_io_equals_upcast_chain(dtype, n, sym, specials):
     assert torch.equal(gmin_a.view(torch.int32), gmin_b.view(torch.int32))
     assert torch.equal(gmax_a.view(torch.int32), gmax_b.view(torch.int32))
     assert bool(torch.isfinite(gmin_a).all()) == all(abs(v) < float("inf") for v in specials)
+
+
+def _lg_backward_raw(x, g, delta, offset, steps, spec_of, offset_elems=0):
+    """aimet_lg_backward (float32) or aimet_lg_backward_16 (fp16 / bf16) on a per-tensor x through the
+    raw C call: (grad_x, sums[3], grad_min, grad_max). spec_of: None (no range gradients) or
+    (emin, emax, sym). offset_elems: the three tensors live in views that many elements into their
+    buffers (1: no 16-B alignment, so every tile takes the element loop)."""
+    from aimet_amd import _native
+    from aimet_amd.learned_grid import _RangeSpec
+    from aimet_amd.tensor_quantizer import IO_DTYPES
+    n = x.numel()
+
+    def view(t):
+        buf = torch.empty(n + offset_elems, dtype=t.dtype, device=DEV)
+        buf[offset_elems:].copy_(t)
+        return buf[offset_elems:]
+
+    xv, gv, gx = view(x), view(g), view(torch.zeros_like(x))
+    assert (xv.data_ptr() % 16 == 0) == (offset_elems == 0)
+    sums = torch.full((3,), float("nan"), device=DEV)
+    gmin, gmax = torch.full((1,), float("nan"), device=DEV), torch.full((1,), float("nan"), device=DEV)
+    spec = None
+    if spec_of is not None:
+        emin, emax, sym = spec_of
+        spec = ctypes.byref(_RangeSpec(emin.data_ptr(), emax.data_ptr(), delta.data_ptr(), gmin.data_ptr(),
+                                       gmax.data_ptr(), int(sym)))
+    s = torch.cuda.current_stream().cuda_stream
+    if x.dtype == torch.float32:
+        _native.call("aimet_lg_backward", xv.data_ptr(), gv.data_ptr(), gx.data_ptr(), sums.data_ptr(), 1, 1, n,
+                     delta.data_ptr(), offset.data_ptr(), ctypes.c_float(steps), spec, s)
+    else:
+        _native.call("aimet_lg_backward_16", xv.data_ptr(), gv.data_ptr(), gx.data_ptr(), sums.data_ptr(), n,
+                     IO_DTYPES[x.dtype], delta.data_ptr(), offset.data_ptr(), ctypes.c_float(steps), spec, s)
+    return gx.clone(), sums, gmin, gmax
+
+
+def _lg_raw_case(n, dtype, sym, seed):
+    """x, grad of `dtype` and a per-tensor 8-bit encoding (delta, offset, steps, emin, emax)."""
+    from aimet_amd.learned_grid import _device_delta_offset
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    x = (torch.randn(n, device=DEV, generator=g) * 3).to(dtype)
+    gr = torch.randn(n, device=DEV, generator=g).to(dtype)
+    emin, emax = torch.tensor([-2.5], device=DEV), torch.tensor([3.25], device=DEV)
+    delta, offset, steps = _device_delta_offset(8, emin, emax, sym, False, False)
+    return x, gr, delta, offset, steps, emin, emax
+
+
+def _i32(t):
+    return t.view(torch.int32)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_learned_grid_backward_16_pipelined_trips_equal_upcast(dtype):
+    """aimet_lg_backward_16 with more than one tile per workgroup: n = 4096 * 4098 + 5 is 4099 tiles
+    over the 2048-workgroup grid, so workgroups 0 and 1 take three tiles (ending in either register
+    buffer), the others two, and the last tile is partial. Without range gradients (mode 0), with a
+    symmetric and with an asymmetric spec: grad_x == aimet_lg_backward on the upcast tensors cast
+    down, the three sums and both range gradients the same bits."""
+    n = 4096 * 4098 + 5
+    for spec_sym in (None, True, False):
+        x, gr, delta, offset, steps, emin, emax = _lg_raw_case(n, dtype, bool(spec_sym), 77)
+        spec = None if spec_sym is None else (emin, emax, spec_sym)
+        gx_a, sums_a, gmin_a, gmax_a = _lg_backward_raw(x, gr, delta, offset, steps, spec)
+        gx_b, sums_b, gmin_b, gmax_b = _lg_backward_raw(x.float(), gr.float(), delta, offset, steps, spec)
+        assert torch.equal(gx_a.view(torch.int16), gx_b.to(dtype).view(torch.int16)), spec_sym
+        assert torch.equal(_i32(sums_a), _i32(sums_b)), (spec_sym, sums_a, sums_b)
+        assert bool(torch.isfinite(sums_a).all())
+        if spec is not None:
+            assert torch.equal(_i32(gmin_a), _i32(gmin_b)) and torch.equal(_i32(gmax_a), _i32(gmax_b)), spec_sym
+            assert bool(torch.isfinite(gmin_a).all() and torch.isfinite(gmax_a).all())
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("asym_spec", [False, True])
+def test_learned_grid_backward_element_path_equals_vector_path(dtype, asym_spec):
+    """The per-tensor backward element by element (views offset by one element: no 16-B alignment,
+    every tile takes the element loop) == the vector path on the same values in aligned buffers:
+    grad_x and the three sums bit for bit, n = 4096 * 3 + 5 (three full tiles and a partial one),
+    without range gradients (mode 0) and with an asymmetric spec (mode 2)."""
+    x, gr, delta, offset, steps, emin, emax = _lg_raw_case(4096 * 3 + 5, dtype, False, 78)
+    spec = (emin, emax, False) if asym_spec else None
+    gx_v, sums_v, _, _ = _lg_backward_raw(x, gr, delta, offset, steps, spec)
+    gx_e, sums_e, _, _ = _lg_backward_raw(x, gr, delta, offset, steps, spec, offset_elems=1)
+    bits_t = torch.int32 if dtype == torch.float32 else torch.int16
+    assert torch.equal(gx_v.view(bits_t), gx_e.view(bits_t))
+    assert torch.equal(_i32(sums_v), _i32(sums_e)), (sums_v, sums_e)
+    assert bool(torch.isfinite(sums_v).all()) and bool((gx_v != 0).any())
 
 
 _LG_FOLD_CHILD = r"""
