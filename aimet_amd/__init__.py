@@ -12,6 +12,8 @@ operator surface on top:
 * ``aimet_amd.adaround``           -- AdaRound soft-rounding autograd on the fused kernels
 * ``aimet_amd.seq_mse``            -- Sequential MSE weight-range search on the fused candidate kernels
 * ``aimet_amd.gptvq``              -- GPTVQ vector weight quantization on the fused k-means / sweep kernels
+* ``aimet_amd.batch_norm_fold``, ``aimet_amd.cross_layer_equalization``, ``aimet_amd.bias_correction``
+                                   -- data-free quantization: BN fold, CLS + high-bias fold, bias correction
 * ``aimet_amd.distributed``        -- calibration sharded over ranks (RCCL stats exchange)
 
 There is no CPU fallback: without libaimet_amd.so or an MI355X every compute call raises.

@@ -86,6 +86,12 @@ class DfqBnFoldJobC(ctypes.Structure):
                 ("forward", ctypes.c_int32)]
 
 
+class BcAnalyticalJobC(ctypes.Structure):
+    """aimet_bc_analytical_job."""
+    _fields_ = [("w", DfqWeightC), ("wq", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("gamma", ctypes.c_void_p),
+                ("beta", ctypes.c_void_p), ("activation", ctypes.c_int32)]
+
+
 # name -> argtypes (restype is int status unless listed in _RESTYPES)
 _PROTOTYPES = {
     "aimet_last_error": [],
@@ -231,6 +237,10 @@ _PROTOTYPES = {
                              ctypes.POINTER(DfqWeightC), _vp, _vp, _vp],
     "aimet_dfq_bias_fold": [_vp, _vp, _vp, _i64, _int, _vp, ctypes.POINTER(DfqWeightC), _vp, _vp],
     "aimet_dfq_launch_count": [_i64p, _int],
+    "aimet_bc_channel_sums": [_vp, _i64, _i64, _i64, _vp, _vp],
+    "aimet_bc_apply_empirical": [_vp, _vp, _vp, _i64, ctypes.c_double, _vp],
+    "aimet_bc_analytical": [ctypes.POINTER(BcAnalyticalJobC), _i64, _vp],
+    "aimet_bc_launch_count": [_i64p, _int],
 }
 _RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p}
 

@@ -268,6 +268,6 @@ def _stub(name):
 
 for _name in ("GetQuantizationInstance", "GetSVDInstance", "Svd", "LayerAttributes", "EqualizationParams",
               "scaleLayerParams", "scaleDepthWiseSeparableLayer", "BNParams", "BNParamsHighBiasFold",
-              "updateBias", "BiasCorrection", "LayerParams", "ModelOpDefParser", "getRescaledOutputAndBias",
+              "updateBias", "BiasCorrection", "BnBasedBiasCorrection", "LayerParams", "ModelOpDefParser", "getRescaledOutputAndBias",
               "str_to_dtype", "str_to_rank"):
     globals()[_name] = _stub(_name)

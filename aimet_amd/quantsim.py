@@ -17,6 +17,7 @@ Deliberately narrower than the reference (SURVEY §8 marks the rest out of scope
   * export writes the PyTorch-named `<prefix>_torch.encodings` file; the ONNX-named
     `<prefix>.encodings` needs an ONNX export of the model, which is outside this core.
 """
+import collections
 import contextlib
 import copy
 import json
@@ -41,6 +42,16 @@ _SCHEME_NAMES = {"tf": QuantScheme.post_training_tf, "tf_enhanced": QuantScheme.
                  "percentile": QuantScheme.post_training_percentile}
 _RANGE_LEARNING = (QuantScheme.training_range_learning_with_tf_init,
                    QuantScheme.training_range_learning_with_tf_enhanced_init)
+
+
+class QuantParams(collections.namedtuple("QuantParams", ["weight_bw", "act_bw", "round_mode", "quant_scheme",
+                                                         "config_file"])):
+    """v1/quantsim.py:103-128: the quantization settings bias correction builds its sim with."""
+    __slots__ = ()
+
+    def __new__(cls, weight_bw: int = 8, act_bw: int = 8, round_mode: str = "nearest",
+                quant_scheme: Union[QuantScheme, str] = QuantScheme.post_training_tf_enhanced, config_file=None):
+        return super().__new__(cls, weight_bw, act_bw, round_mode, quant_scheme, config_file)
 
 
 def get_v1_quant_scheme_for_initialization(quant_scheme: QuantScheme) -> QuantScheme:

@@ -837,6 +837,43 @@ int aimet_dfq_bias_fold(const float* gamma, const float* beta, const float* scal
 /* Kernel launches the four entry points above have issued in this process; reset != 0 zeroes it. */
 int aimet_dfq_launch_count(int64_t* count, int reset);
 
+/* ---- bias correction (aimet_torch/bias_correction.py, aimet_common/bias_correction.py) -----------
+ * Device pointers throughout, fp32 tensors and parameters, double sums. No atomics: the order of
+ * every addition is fixed by the sizes and the base alignment, so equal inputs give equal bits. */
+
+/* acc_dev[c] += sum over o < outer, i < inner of (double) x[o][c][i], x contiguous [outer][C][inner].
+ * NCHW layer outputs are (N, C, H*W); Linear and channels-last outputs are (rows, C, 1). One read of
+ * x; two launches (per-(split, channel) partials, then their fold in order into acc_dev). At most
+ * 2^31 - 1 elements per channel. */
+int aimet_bc_channel_sums(const float* x, int64_t outer, int64_t C, int64_t inner, double* acc_dev, void* stream);
+
+/* bias[c] = (float) ((double) bias[c] - (q_sum[c] - ref_sum[c]) / count): the mean per-channel
+ * difference of the quantized and the reference output, count elements per channel. */
+int aimet_bc_apply_empirical(float* bias, const double* ref_sum, const double* q_sum, int64_t C, double count,
+                             void* stream);
+
+/* One analytical (BN-based) correction. wq has w's layout and holds the quantize-dequantized weight.
+ * eps[o,i] = sum_j (wq[o,i,j] - w[o,i,j]) (each difference rounded to fp32, the sum in double);
+ * E[i] = E[act(N(beta[i], gamma[i]^2))] for activation 0 (none: beta), 1 (ReLU) or 2 (ReLU6), in
+ * double through erfc, gamma used as given (its sign kept, gamma == 0 by IEEE rules); gamma and beta
+ * both NULL: ones and zeros. w.cin > 1: err[o] = sum_i eps[o,i] * E[i]; w.cin == 1 (depthwise):
+ * err[o] = eps[o,0] * E[o]. bias[o] = (float) ((double) bias[o] - err[o]). */
+typedef struct aimet_bc_analytical_job
+{
+    aimet_dfq_weight w;
+    const float* wq;
+    float* bias;
+    const float* gamma;
+    const float* beta;
+    int32_t activation;
+} aimet_bc_analytical_job;
+
+/* `count` corrections (host table, no two on the same bias) in one launch, grid (job, output channel). */
+int aimet_bc_analytical(const aimet_bc_analytical_job* jobs, int64_t count, void* stream);
+
+/* Kernel launches the three entry points above have issued in this process; reset != 0 zeroes it. */
+int aimet_bc_launch_count(int64_t* count, int reset);
+
 #ifdef __cplusplus
 }
 #endif
