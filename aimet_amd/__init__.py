@@ -14,6 +14,7 @@ operator surface on top:
 * ``aimet_amd.gptvq``              -- GPTVQ vector weight quantization on the fused k-means / sweep kernels
 * ``aimet_amd.batch_norm_fold``, ``aimet_amd.cross_layer_equalization``, ``aimet_amd.bias_correction``
                                    -- data-free quantization: BN fold, CLS + high-bias fold, bias correction
+* ``aimet_amd.quant_analyzer``     -- QuantAnalyzer: sensitivity, ranges, histograms, per-layer MSE on a fused kernel
 * ``aimet_amd.distributed``        -- calibration sharded over ranks (RCCL stats exchange)
 
 There is no CPU fallback: without libaimet_amd.so or an MI355X every compute call raises.
@@ -21,6 +22,7 @@ There is no CPU fallback: without libaimet_amd.so or an MI355X every compute cal
 from aimet_amd import _native  # noqa: F401
 from aimet_amd.libpymo import QuantizationMode, RoundingMode, TfEncoding  # noqa: F401
 from aimet_amd.tensor_quantizer import AimetTensorQuantizer  # noqa: F401
+from aimet_amd.quant_analyzer import CallbackFunc, QuantAnalyzer  # noqa: F401
 
 __version__ = "0.1.0"
 

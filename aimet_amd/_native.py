@@ -241,6 +241,8 @@ _PROTOTYPES = {
     "aimet_bc_apply_empirical": [_vp, _vp, _vp, _i64, ctypes.c_double, _vp],
     "aimet_bc_analytical": [ctypes.POINTER(BcAnalyticalJobC), _i64, _vp],
     "aimet_bc_launch_count": [_i64p, _int],
+    "aimet_qa_sq_err": [_vp, _vp, _i64, _int, ctypes.c_double, _vp, _vp],
+    "aimet_qa_launch_count": [_i64p, _int],
 }
 _RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p}
 

@@ -874,6 +874,21 @@ int aimet_bc_analytical(const aimet_bc_analytical_job* jobs, int64_t count, void
 /* Kernel launches the three entry points above have issued in this process; reset != 0 zeroes it. */
 int aimet_bc_launch_count(int64_t* count, int reset);
 
+/* ---- QuantAnalyzer (aimet_torch/v1/quant_analyzer.py export_per_layer_mse_loss) --------------------
+ * acc_dev[0] += scale * sum_i ((double) ref[i] - (double) x[i])^2 and
+ * acc_dev[1] += scale * sum_i ((double) ref[i])^2 over two device tensors of n elements (1 .. 2^40)
+ * and one dtype: io_dtype 0 = float32, 1 = float16, 2 = bfloat16 (the 16-bit values as in
+ * aimet_qdq_per_tensor_16). Every element is widened to double before the subtraction; squares and
+ * sums are double. ref and x aligned to their element size, acc_dev to 8 bytes; 16-byte loads when
+ * ref and x are equally misaligned to 16 bytes, element loads otherwise. One read of each tensor, two
+ * launches (per-workgroup partials, then their fold in a fixed order, times scale, into acc_dev); no
+ * atomics, so equal pointers and sizes give equal bits. */
+int aimet_qa_sq_err(const void* ref, const void* x, int64_t n, int io_dtype, double scale, double* acc_dev,
+                    void* stream);
+
+/* Kernel launches aimet_qa_sq_err has issued in this process; reset != 0 zeroes it. */
+int aimet_qa_launch_count(int64_t* count, int reset);
+
 #ifdef __cplusplus
 }
 #endif
