@@ -17,7 +17,10 @@ the rounding loss as a separate autograd graph. The rounding-loss VALUE is accum
 The loop is launch-bound for MobileNet-sized layers, so by default one iteration is captured in a
 HIP graph and replayed (batch indices drawn up front in the eager loop's order, the annealed beta
 read from device memory, Adam capturable); depthwise convolutions run on PyTorch's native kernels
-(3-5x faster than MIOpen's here). MobileNet-v2, 53 layers: 0.47 ms -> 0.19 ms per iteration.
+(3-5x faster than MIOpen's here). MobileNet-v2, 53 layers: 0.0545 ms per iteration
+(profiles/r05/adaround_mobilenet_10k.json). plan_loop picks a layer's form from its shapes alone, the
+form's builder (_STEP_BUILDERS) the buffers and launches of one iteration around the shared
+_LoopState, _run_captured captures and replays them.
 
 Data parallel (adaround_optimizer.py:139-160,214-216), when torch.distributed is initialised (or a
 group is given): the cached samples are sharded rank::world, Adam's learning rate is multiplied by
@@ -29,6 +32,7 @@ the collective between them: [forward + backward] -> all_reduce(alpha.grad) -> [
 """
 import contextlib
 import logging
+import math
 import warnings
 from dataclasses import dataclass
 from typing import Callable, Optional, Tuple
@@ -98,18 +102,6 @@ def conv_backend(module: torch.nn.Module):
 # the same alpha. The module-level switches below select between forms that the tests compare
 # (tests/test_adaround_wrapper.py patches them); none is read from the environment.
 
-# 1x1 convolutions and linear layers of the fused AdaRound loop as direct GEMMs (torch.matmul /
-# hipBLASLt) instead of MIOpen convolutions through autograd
-_GEMM_LAYERS = True
-# 1x1 / linear layers have two loop forms that sum the weight gradient in different orders (GEMM or
-# MIOpen convolution through autograd), so the optimised alpha depends on the form: "gemm" (the
-# rule) or "autograd" (the convolution form, the GEMM form's fallback when it cannot be captured)
-_LOOP_FORM = "gemm"
-# the pointwise / im2col weight gradient: "bmm" (per-sample GEMMs + a sum over the batch) or "mm"
-# (one GEMM over (n, hw) from channel-major copies); "auto" takes mm for spatial sizes <= 64
-# (MobileNet-v2's 7x7 layers: up to 0.047 ms per iteration less) and bmm above
-# (profiles/r03/adaround_pw_grad_forms.txt)
-_PW_GRAD = "auto"
 # depthwise layers: the whole iteration up to dL/dWq as one pass over the cached rows
 # (aimet_adaround_dw_step, bit-identical to gather + forward + reconstruction gradient + weight
 # gradient); False runs those four launches instead (the tests' comparison)
@@ -130,14 +122,6 @@ _DW_FOLD_ADAM = True
 # (aimet_adaround_pw_step_uses_mfma; the VALU form is slower than the GEMM form there); below 28 x 28
 # the channel-major GEMMs stay faster. "all": every eligible layer, "0": none.
 _PW_FUSED = "auto"
-# the GEMM form of 1x1 layers with channel-major batches (aimet_adaround_gather_cm: x as [C_in][nb hw],
-# so q = W x and dL/dW = g x^T are ONE GEMM each, no per-sample GEMMs, batch sum or transposes), for
-# layers of <= 14 x 14 positions (MobileNet-v2: 0.117 -> 0.063 ms per iteration at 576 -> 96 x 14^2;
-# slower at 28^2: 0.071 -> 0.09); False: the [nb][C][hw] batches with per-sample GEMMs (_PW_GRAD)
-# everywhere. (The same form on the f32 matrix cores in two kernels of our own, and the weight
-# gradient as split-K GEMM slices, measured slower and are not in the library:
-# tools/studies/pw_cm_mfma.hip, profiles/r04/pw_cm_*.jsonl.)
-_PW_CM = True
 # iterations per captured HIP graph in the single-process loop: one hipGraphLaunch per iteration
 # left the GPU waiting on the host between replays for small layers (a depthwise layer's ~10 us of
 # kernels per iteration in a ~100 us window, profiles/r04/adaround_loop_summary.txt); the counters and
@@ -164,21 +148,22 @@ _IM2COL_MAX_K = 64
 _IM2COL_MAX_BYTES = 8 << 30
 
 
-def _im2col_ok(module: torch.nn.Module, inp_data: torch.Tensor) -> bool:
+def _im2col_ok(module: torch.nn.Module, in_shape, itemsize: int) -> bool:
     """A groups-1 Conv2d (not 1x1 / stride 1, which _is_pointwise runs directly) whose
-    C_in * kh * kw <= _IM2COL_MAX_K and whose unfolded input cache fits _IM2COL_MAX_BYTES: its
-    loop runs as the pointwise form on the unfolded cache (deterministic GEMMs; MIOpen's
-    deterministic stem solutions were 4x slower than its default ones)."""
+    C_in * kh * kw <= _IM2COL_MAX_K and whose unfolded input cache (in_shape: the cache's
+    [N, C_in, H, W]) fits _IM2COL_MAX_BYTES: its loop runs as the pointwise form on the unfolded
+    cache (deterministic GEMMs; MIOpen's deterministic stem solutions were 4x slower than its
+    default ones)."""
     if not isinstance(module, torch.nn.Conv2d) or module.groups != 1 or _is_pointwise(module) \
-            or module.padding_mode != "zeros" or isinstance(module.padding, str) or inp_data.dim() != 4:
+            or module.padding_mode != "zeros" or isinstance(module.padding, str) or len(in_shape) != 4:
         return False
     kdim = module.in_channels * module.kernel_size[0] * module.kernel_size[1]
     if kdim > _IM2COL_MAX_K:
         return False
-    h, w = inp_data.shape[2], inp_data.shape[3]
+    h, w = in_shape[2], in_shape[3]
     oh = (h + 2 * module.padding[0] - module.dilation[0] * (module.kernel_size[0] - 1) - 1) // module.stride[0] + 1
     ow = (w + 2 * module.padding[1] - module.dilation[1] * (module.kernel_size[1] - 1) - 1) // module.stride[1] + 1
-    return inp_data.shape[0] * kdim * oh * ow * inp_data.element_size() <= _IM2COL_MAX_BYTES
+    return in_shape[0] * kdim * oh * ow * itemsize <= _IM2COL_MAX_BYTES
 
 
 def depthwise_spec(module: torch.nn.Module):
@@ -244,21 +229,15 @@ class _BoundSoftQuant:
         self.d, self.o = d.contiguous(), o.contiguous()
         self.bw = int(bitwidth)
         self.loss = round_loss_out
-        P = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
-        self.pw, self.pa = P(self.w), P(alpha)
-        self.pd, self.po = P(self.d), P(self.o)
-        self.pl = P(round_loss_out) if round_loss_out is not None else None
+        self.pw, self.pa, self.pd, self.po = _ptr(self.w), _ptr(alpha), _ptr(self.d), _ptr(self.o)
+        self.pl = _ptr(round_loss_out) if round_loss_out is not None else None
         self.reg = self.beta = 0.0
         self.reg_beta = None   # graph mode: device tensor [reg, beta, beta - 1] read by the backward kernel
-
-    def _stream(self):
-        # the current stream at call time: a HIP-graph capture runs on torch's capture stream
-        return ctypes.c_void_p(torch.cuda.current_stream(self.w.device).cuda_stream)
 
     def forward(self):
         wq = torch.empty_like(self.w)    # fresh outputs: autograd may keep / steal them
         rc = self.fwd(self.pw, self.pa, ctypes.c_void_p(wq.data_ptr()), *self.shape, self.pd, self.po, self.bw, 1,
-                      self._stream())
+                      _stream_ptr(self.w.device))
         if rc:
             _native.check(rc)
         return wq
@@ -269,11 +248,11 @@ class _BoundSoftQuant:
         if self.reg_beta is not None:
             rc = self.bwd_dev(self.pw, self.pa, ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(ga.data_ptr()),
                               *self.shape, self.pd, self.po, self.bw, ctypes.c_void_p(self.reg_beta.data_ptr()),
-                              self.pl, self._stream())
+                              self.pl, _stream_ptr(self.w.device))
         else:
             rc = self.bwd(self.pw, self.pa, ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(ga.data_ptr()),
                           *self.shape, self.pd, self.po, self.bw, ctypes.c_double(self.reg), ctypes.c_double(self.beta),
-                          self.pl if self.reg != 0.0 else None, self._stream())
+                          self.pl if self.reg != 0.0 else None, _stream_ptr(self.w.device))
         if rc:
             _native.check(rc)
         return ga
@@ -329,10 +308,367 @@ def _finish_alpha(alpha, alpha_init):
     return alpha_init
 
 
+def _loop_setup(module, delta, offset, ch_axis, alpha_init):
+    """(weight, device, delta, offset, alpha) of a layer's loop, the encoding as flat float32 vectors."""
+    w = module.weight.detach()
+    shape = [1] * w.dim()
+    shape[ch_axis] = -1
+    d = torch.as_tensor(delta, dtype=torch.float32, device=w.device).reshape(-1).contiguous()
+    o = torch.as_tensor(offset, dtype=torch.float32, device=w.device).reshape(-1).contiguous()
+    return w, w.device, d, o, _starting_alpha(w, d, shape, alpha_init)
+
+
+def _torch_adam(alpha, world, **kw):
+    # one Adam kernel per step (the reference's default multi-tensor Adam: same update rule); the
+    # learning rate scaled by the world size (adaround_optimizer.py:155-158)
+    try:
+        return torch.optim.Adam([alpha], lr=1e-3 * world, fused=True, **kw)
+    except (RuntimeError, TypeError):
+        return torch.optim.Adam([alpha], lr=1e-3 * world, **kw)
+
+
+@dataclass(frozen=True)
+class LoopPlan:
+    """The fused loop's form for one layer (plan_loop)."""
+    form: str                       # what last_loop_form reports
+    fallback: Optional[str] = None  # the form to run when `form` cannot be captured
+    indexed: bool = False           # the reconstruction gradient reads the fp target in place
+    C_out: int = 1
+    hw: int = 1                     # output positions per channel
+    cin: int = 0                    # GEMM forms: the inner dimension (C_in, or C_in k k unfolded)
+    dw: Optional[Tuple[int, int, int, int]] = None   # depthwise (K, stride, pad, dil)
+
+
+def plan_loop(module, in_shape, in_dtype, out_shape, out_dtype, act_func, aligned: bool) -> LoopPlan:
+    """The form of the fused loop for `module` on caches of these shapes ([N, ...]) and dtypes.
+    aligned: the caches the loop reads start on 16-byte boundaries."""
+    # A pure function of its arguments and the switches above: nothing is allocated or launched
+    # (aimet_adaround_pw_step_uses_mfma is a host-only query).
+    # The fused reconstruction gradient reads the fp target in place (no gathered copy) when it
+    # has a fused form: [N, C, ...] float32 outputs, ReLU / ReLU6 / no activation
+    indexed = _act_code(act_func) is not None and len(out_shape) >= 2 and out_dtype == torch.float32
+    if not indexed:
+        return LoopPlan("autograd")
+    C_out, hw = out_shape[1], math.prod(out_shape[2:])
+    if len(out_shape) == 4 and _im2col_ok(module, in_shape, in_dtype.itemsize):
+        # the cached inputs unfolded once ([N, C_in k k, OH OW]): a pointwise problem
+        form, cin, hw_in = "im2col", in_shape[1] * module.kernel_size[0] * module.kernel_size[1], hw
+    elif depthwise_spec(module) is not None and len(in_shape) == 4:
+        return LoopPlan("dw", None, True, C_out, hw, dw=depthwise_spec(module))
+    elif _is_pointwise(module) and len(in_shape) == 4:
+        form, cin, hw_in = "pointwise", in_shape[1], in_shape[2] * in_shape[3]
+    elif isinstance(module, torch.nn.Linear) and len(in_shape) == 2:
+        return LoopPlan("linear", "autograd", True, C_out, hw)
+    else:
+        return LoopPlan("autograd", None, True, C_out, hw)
+    wanted = _PW_FUSED == "all" or (_PW_FUSED != "0" and hw >= 28 * 28 and (
+        not (cin > C_out and hw < 56 * 56) or (cin >= 32 and _pw_step_uses_mfma(cin, C_out))))
+    if wanted and cin <= 192 and hw_in == hw and hw % 4 == 0 and aligned:
+        form += "_fused"
+    elif hw <= 14 * 14:
+        form += "_cm"
+    # 1x1 and linear layers have a second form (MIOpen through autograd) that sums the weight
+    # gradient in another order: it runs only when the first cannot be captured
+    return LoopPlan(form, "autograd" if form.startswith("pointwise") else None, True, C_out, hw, cin)
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _stream_ptr(dev):
+    # the current stream at call time: a HIP-graph capture runs on torch's capture stream
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+_ADAM = tuple(ctypes.c_double(v) for v in (1e-3, 0.9, 0.999, 1e-8))   # lr, beta1, beta2, eps
+_CHUNK = 500   # iterations per host draw of batch indices (_drawer)
+
+
+class _LoopState:
+    """What every form of the fused loop shares, built once per layer."""
+    # alpha and its Adam moments, the device-side iteration counters [it_cur, it_next], the batch
+    # table idx_all, the {reg, beta, beta - 1} table rb_all, Adam's bias corrections, the
+    # soft-quantized weight wq and the caches. A form's builder (_STEP_BUILDERS) adds its own
+    # buffers and returns its step(stream): the launches of one iteration.
+
+    def __init__(self, plan, module, inp_data, out_data, sq, iters, idx_all, rb_all, act_func, round_loss_out):
+        self.plan, self.module, self.sq, self.alpha, self.dev = plan, module, sq, sq.alpha, sq.w.device
+        self.inp_data, self.out_data, self.iters, self.nb = inp_data, out_data, iters, idx_all.shape[1]
+        self.idx_all, self.rb_all, self.act_func, self.loss = idx_all, rb_all, act_func, round_loss_out
+        self.lib = _native.load()
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.alpha), torch.zeros_like(self.alpha)
+        self.counters = torch.zeros(2, dtype=torch.long, device=self.dev)
+        self.it_cur = ctypes.c_void_p(self.counters.data_ptr())
+        self.it_next = ctypes.c_void_p(self.counters.data_ptr() + 8)
+        self.wq = torch.empty_like(sq.w).requires_grad_(True)
+        # Adam's bias corrections for every step of the loop, computed once (the same device
+        # arithmetic the step would run per wave: same bits)
+        self.bias_corr = torch.empty(iters, 2, dtype=torch.float32, device=self.dev)
+        _native.check(self.lib.aimet_adaround_adam_bias_corrections(_ADAM[1], _ADAM[2], iters, _ptr(self.bias_corr),
+                                                                    _stream_ptr(self.dev)))
+        self.code = _act_code(act_func)
+        self.bias = module.bias.detach().contiguous() if module.bias is not None else None
+        self.pbias = _ptr(self.bias) if self.bias is not None else None
+        self.alpha0 = self.alpha.detach().clone()
+        self.loss0 = round_loss_out.clone() if round_loss_out is not None else None
+
+    def adam_step(self, s, grad, nparts=1, part_kk=0):
+        # dL/dalpha from dL/dWq (`grad`: nparts ordered slices of it part_kk floats apart, summed
+        # here) + the Adam update; it also writes the next iteration's soft-quantized weight into
+        # wq (it reads W and the new alpha anyway): no separate forward launch per iteration
+        sq = self.sq
+        _native.check(self.lib.aimet_adaround_backward_adam_parts(
+            sq.pw, sq.pa, _ptr(grad), nparts, part_kk, _ptr(self.exp_avg), _ptr(self.exp_avg_sq), *sq.shape, sq.pd,
+            sq.po, sq.bw, _ptr(self.rb_all), self.it_next, self.it_cur, *_ADAM, sq.pl, _ptr(self.wq),
+            _ptr(self.bias_corr), s))
+
+    def soft_weight(self):   # wq from the current alpha (before the first iteration)
+        sq = self.sq
+        _native.check(sq.fwd(sq.pw, sq.pa, _ptr(self.wq), *sq.shape, sq.pd, sq.po, sq.bw, 1, _stream_ptr(self.dev)))
+
+    def restart(self):   # back to iteration 0
+        with torch.no_grad():
+            self.alpha.copy_(self.alpha0)
+            self.exp_avg.zero_()
+            self.exp_avg_sq.zero_()
+            self.counters.zero_()
+            if self.loss is not None:
+                self.loss.copy_(self.loss0)
+        self.soft_weight()
+
+    def batch_like(self, cache, dtype=None):
+        return torch.empty((self.nb,) + tuple(cache.shape[1:]), dtype=dtype or cache.dtype, device=self.dev)
+
+    def batch_buffers(self):   # the gathered input rows, the layer output q and dL/dq
+        q = self.batch_like(self.out_data, torch.float32)
+        return self.batch_like(self.inp_data), q, torch.empty_like(q)
+
+    def gather(self, s, inp, target=None):   # this iteration's cache rows; it_next moves here
+        _native.check(self.lib.aimet_adaround_gather(
+            _ptr(self.inp_data), _ptr(self.out_data), _ptr(inp), _ptr(target) if target is not None else None,
+            _ptr(self.idx_all), self.it_cur, self.it_next, self.nb, inp[0].numel(), self.out_data[0].numel(), s))
+
+    def recon_grad(self, s, q, g, with_bias):   # g = dL/dq, the target rows read in place
+        p = self.plan
+        _native.check(self.lib.aimet_adaround_recon_grad_indexed(
+            _ptr(q), _ptr(self.out_data), _ptr(self.idx_all), self.it_cur, _ptr(g), self.nb, p.C_out, p.hw,
+            self.pbias if with_bias else None, self.code, s))
+
+
+def _workspace(st, query, *dims):
+    n = ctypes.c_int64()
+    _native.check(query(*dims, ctypes.byref(n)))
+    return torch.empty(n.value, dtype=torch.float32, device=st.dev)
+
+
+# The iteration up to dL/dWq as one pass (aimet_adaround_dw_step / _pw_step): the batch read in
+# place from the caches, q and g never stored; it_next moves in the pass. parts: the weight-gradient
+# slices in ws as adam_step's (grad, nparts, part_kk), which then folds them (one launch fewer, the
+# same sum); None: the pass folds them itself, in a launch of its own.
+def _one_pass_step(st, kernel, dims, ws, parts):
+    grad = parts or (torch.empty_like(st.sq.w),)
+    gw = None if parts else _ptr(grad[0])
+
+    def step(s):
+        _native.check(kernel(_ptr(st.inp_data), _ptr(st.out_data), _ptr(st.idx_all), st.it_cur, st.it_next,
+                             _ptr(st.wq), st.pbias, gw, _ptr(ws), *dims, st.code, s))
+        st.adam_step(s, *grad)
+    return step
+
+
+# Depthwise layers on the native kernels, no autograd: the one-pass step, or (_DW_FUSED off, its
+# comparison) gather + forward + reconstruction gradient + weight gradient.
+def _dw_step(st):
+    lib, nb, (K, stride, pad, dil) = st.lib, st.nb, st.plan.dw
+    (C, H, W), (OH, OW) = st.inp_data.shape[1:], st.out_data.shape[2:]
+    dims = (nb, C, H, W, OH, OW, K, stride, pad, dil)
+    ws = _workspace(st, lib.aimet_dwconv2d_grad_weight_workspace, nb, C, OH, OW, K)
+    if _DW_FUSED:
+        slices = ctypes.c_int64()
+        if _DW_FOLD_ADAM:
+            _native.check(lib.aimet_adaround_dw_step_slices(_ptr(st.out_data), nb, C, OH, OW, K, stride, dil,
+                                                            ctypes.byref(slices)))
+        return _one_pass_step(st, lib.aimet_adaround_dw_step, dims, ws,
+                              (ws, slices.value, K * K) if slices.value else None)
+    inp, q, g = st.batch_buffers()
+    gw = torch.empty_like(st.sq.w)
+
+    def step(s):
+        st.gather(s, inp)
+        _native.check(lib.aimet_dwconv2d_forward(_ptr(inp), _ptr(st.wq), st.pbias, _ptr(q), *dims, s))
+        st.recon_grad(s, q, g, False)
+        _native.check(lib.aimet_dwconv2d_grad_weight(_ptr(inp), _ptr(g), _ptr(gw), _ptr(ws), *dims, s))
+        st.adam_step(s, gw)
+    return step
+
+
+# 1x1 layers / the unfolded stem with few input channels (plan_loop's _PW_FUSED rule): one pass.
+def _pw_one_pass_step(st):
+    dims = (st.nb, st.plan.cin, st.plan.C_out, st.plan.hw)
+    ws, parts = _workspace(st, st.lib.aimet_adaround_pw_step_workspace, *dims), None
+    if _DW_FOLD_ADAM:
+        off, nsl = ctypes.c_int64(), ctypes.c_int64()
+        _native.check(st.lib.aimet_adaround_pw_step_slices(*dims, ctypes.byref(off), ctypes.byref(nsl)))
+        parts = (ws[off.value:], nsl.value, st.sq.w.numel())
+    return _one_pass_step(st, st.lib.aimet_adaround_pw_step, dims, ws, parts)
+
+
+# 1x1 layers of <= 14 x 14 positions as GEMMs over channel-major batches (aimet_adaround_gather_cm:
+# x as [C_in][nb hw], so q = W x and dL/dW = g x^T are ONE GEMM each, no per-sample GEMMs, batch
+# sum or transposes). MobileNet-v2: 0.117 -> 0.063 ms per iteration at 576 -> 96 x 14^2; slower at
+# 28^2: 0.071 -> 0.09. (The same form on the f32 matrix cores in two kernels of our own, and the
+# weight gradient as split-K GEMM slices, measured slower and are not in the library:
+# tools/studies/pw_cm_mfma.hip, profiles/r04/pw_cm_*.jsonl.)
+def _cm_step(st):
+    lib, p, nb = st.lib, st.plan, st.nb
+    x = torch.empty((p.cin, nb * p.hw), dtype=torch.float32, device=st.dev)
+    q = torch.empty((p.C_out, nb * p.hw), dtype=torch.float32, device=st.dev)
+    g = torch.empty_like(q)
+
+    def step(s):
+        _native.check(lib.aimet_adaround_gather_cm(_ptr(st.inp_data), _ptr(x), _ptr(st.idx_all), st.it_cur, st.it_next,
+                                                   nb, p.cin, p.hw, s))
+        torch.mm(st.wq.detach().view(p.C_out, -1), x, out=q)
+        _native.check(lib.aimet_adaround_recon_grad_indexed_cm(_ptr(q), _ptr(st.out_data), _ptr(st.idx_all), st.it_cur,
+                                                               _ptr(g), nb, p.C_out, p.hw, st.pbias, st.code, s))
+        st.adam_step(s, torch.mm(g, x.t()))
+    return step
+
+
+# The other 1x1 layers (or unfolded stems) as one batched GEMM per direction (hipBLASLt, no
+# NCHW<->NHWC transposes): q[n] = Wq @ x[n], dL/dWq = sum_n g[n] @ x[n]^T; the bias is added inside
+# the reconstruction kernel.
+def _gemm_step(st):
+    p, nb = st.plan, st.nb
+    inp, q, g = st.batch_buffers()
+    x3, q3, g3 = inp.view(nb, p.cin, -1), q.view(nb, p.C_out, -1), g.view(nb, p.C_out, -1)
+
+    def step(s):
+        st.gather(s, inp)
+        torch.matmul(st.wq.detach().view(p.C_out, -1), x3, out=q3)
+        st.recon_grad(s, q, g, True)
+        st.adam_step(s, torch.matmul(g3, x3.transpose(1, 2)).sum(0))
+    return step
+
+
+# `build` on the input cache unfolded once ([N, C_in k k, OH OW]): each iteration's batch of a
+# small-C_in convolution is then a pointwise problem, gathered by rows like any other.
+def _unfolded(build):
+    def build_im2col(st):
+        m = st.module
+        st.inp_data = F.unfold(st.inp_data, m.kernel_size, m.dilation, m.padding, m.stride).contiguous()
+        return build(st)
+    return build_im2col
+
+
+def _linear_step(st):
+    inp, q, g = st.batch_buffers()
+
+    def step(s):
+        st.gather(s, inp)
+        torch.mm(inp, st.wq.detach().t(), out=q)
+        st.recon_grad(s, q, g, True)
+        st.adam_step(s, torch.mm(g.t(), inp))
+    return step
+
+
+# Any layer through layer_forward and autograd (MIOpen convolutions): the reconstruction gradient
+# from the fused kernel when it has a fused form (indexed), else from torch ops on a gathered target.
+def _autograd_step(st):
+    inp = st.batch_like(st.inp_data)
+    if st.plan.indexed:
+        g = st.batch_like(st.out_data, torch.float32)
+
+        def step(s):
+            st.gather(s, inp)
+            q_out = layer_forward(st.module, inp, st.wq)
+            st.recon_grad(s, q_out, g, False)
+            (gw,) = torch.autograd.grad(q_out, st.wq, grad_outputs=g)
+            st.adam_step(s, gw.contiguous())
+        return step
+    target, act = st.batch_like(st.out_data), st.act_func
+
+    def step(s):
+        st.gather(s, inp, target)
+        q_out = layer_forward(st.module, inp, st.wq)
+        qa, ta = (act(q_out), act(target)) if act is not None else (q_out, target)
+        (gw,) = torch.autograd.grad(recon_loss(qa, ta), st.wq)
+        st.adam_step(s, gw.contiguous())
+    return step
+
+
+_STEP_BUILDERS = {
+    "autograd": _autograd_step, "linear": _linear_step, "dw": _dw_step,
+    "pointwise": _gemm_step, "pointwise_cm": _cm_step, "pointwise_fused": _pw_one_pass_step,
+    "im2col": _unfolded(_gemm_step), "im2col_cm": _unfolded(_cm_step), "im2col_fused": _unfolded(_pw_one_pass_step),
+}
+
+
+def _replay_chunks(iters, draw, replay, dev):
+    """replay(count) over all iterations, a chunk at a time: the next chunk's batches are drawn on
+    the host while the GPU replays this one."""
+    for a in range(0, iters, _CHUNK):
+        b = min(a + _CHUNK, iters)
+        if b < iters:
+            draw(b, min(b + _CHUNK, iters))
+        replay(b - a)
+    torch.cuda.current_stream(dev).synchronize()
+
+
+def _run_captured(st, draw):
+    """Builds the plan's step (its fallback form when the first cannot be captured), captures one
+    and _GRAPH_ITERS iterations in HIP graphs and replays them; returns the form that ran."""
+    dev, iters = st.dev, st.iters
+
+    def capture(step, k=1):
+        # warm-up on a side stream (library handles, allocator, autograd), then capture
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side), torch.enable_grad():
+            st.soft_weight()
+            for _ in range(min(2, iters)):
+                step(_stream_ptr(dev))
+        torch.cuda.current_stream(dev).wait_stream(side)
+        st.restart()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g), torch.enable_grad():
+            for _ in range(k):   # k consecutive iterations (the counters advance on the device)
+                step(_stream_ptr(dev))
+        return g
+
+    form, step = st.plan.form, _STEP_BUILDERS[st.plan.form](st)
+    try:
+        graph = capture(step)
+    except RuntimeError:
+        if st.plan.fallback is None:
+            raise
+        form, step = st.plan.fallback, _STEP_BUILDERS[st.plan.fallback](st)
+        graph = capture(step)
+    k = min(_GRAPH_ITERS, _CHUNK)
+    graph_k = None
+    if k > 1 and iters >= k:
+        # when k iterations cannot be captured (graph-pool memory, an autograd form) the
+        # one-iteration graph runs them, the same results
+        with contextlib.suppress(RuntimeError):
+            graph_k = capture(step, k)
+        st.restart()
+
+    def replay(count):
+        done = 0
+        while graph_k is not None and done + k <= count:
+            graph_k.replay()
+            done += k
+        for _ in range(done, count):
+            graph.replay()
+    _replay_chunks(iters, draw, replay, dev)
+    return form
+
+
 class AdaroundOptimizer:
     """v1/adaround/adaround_optimizer.py."""
 
-    last_loop_form = None   # the layer form the last fused loop ran (dw / pointwise / im2col / linear / autograd)
+    last_loop_form = None   # the form the last fused loop ran (LoopPlan.form, or its fallback)
     is_activation_caching_enabled = True
 
     # ---- the reference's caller surface (v1/adaround/adaround_optimizer.py:69-260) -------------
@@ -475,20 +811,8 @@ class AdaroundOptimizer:
     @staticmethod
     def _optimize_eager(module, inp_data, out_data, delta, offset, bitwidth, ch_axis, opt_params, act_func,
                         generator, round_loss_out, world=1, group=None, alpha_init=None):
-        w = module.weight.detach()
-        dev = w.device
-        shape = [1] * w.dim()
-        shape[ch_axis] = -1
-        d = torch.as_tensor(delta, dtype=torch.float32, device=dev).reshape(-1)
-        o = torch.as_tensor(offset, dtype=torch.float32, device=dev).reshape(-1)
-        alpha = _starting_alpha(w, d, shape, alpha_init)
-        # one Adam kernel per step (the reference's default multi-tensor Adam: same update rule); the
-        # learning rate scaled by the world size (adaround_optimizer.py:155-158)
-        lr = 1e-3 * world
-        try:
-            optimizer = torch.optim.Adam([alpha], lr=lr, fused=True)
-        except (RuntimeError, TypeError):
-            optimizer = torch.optim.Adam([alpha], lr=lr)
+        w, dev, d, o, alpha = _loop_setup(module, delta, offset, ch_axis, alpha_init)
+        optimizer = _torch_adam(alpha, world)
         sq = _BoundSoftQuant(w, alpha, d, o, bitwidth, ch_axis, round_loss_out)
         n = inp_data.shape[0]
         warm = opt_params.num_iterations * opt_params.warm_start
@@ -525,7 +849,8 @@ class AdaroundOptimizer:
             h = torch.stack([torch.randperm(n, generator=generator)[:BATCH_SIZE] for _ in range(a, b)]).pin_memory()
             idx_all[a:b].copy_(h, non_blocking=True)
             staged.append(h)
-        return idx_all, draw, staged
+        draw(0, min(_CHUNK, iters))
+        return idx_all, draw
 
     @staticmethod
     def _reg_beta_all(opt_params, iters, dev):
@@ -542,280 +867,20 @@ class AdaroundOptimizer:
     def _optimize_fused_graph(module, inp_data, out_data, delta, offset, bitwidth, ch_axis, opt_params, act_func,
                               generator, round_loss_out, alpha_init=None):
         """Single-process HIP-graph loop with the iteration's bookkeeping fused into two kernels:
-        aimet_adaround_gather (the batch draw: index lookup + both row gathers, for the four
-        index_select kernels) and aimet_adaround_backward_adam (dL/dalpha + torch's fused-Adam
-        update of alpha in place, for the backward + gradient zero / accumulate + three Adam
-        kernels). The iteration counter and Adam moments live in device memory; the weight
-        gradient comes from torch.autograd.grad (no accumulation into a .grad)."""
-        w = module.weight.detach()
-        dev = w.device
-        shape = [1] * w.dim()
-        shape[ch_axis] = -1
-        d = torch.as_tensor(delta, dtype=torch.float32, device=dev).reshape(-1).contiguous()
-        o = torch.as_tensor(offset, dtype=torch.float32, device=dev).reshape(-1).contiguous()
-        alpha = _starting_alpha(w, d, shape, alpha_init)
+        the batch draw (aimet_adaround_gather, or inside a one-pass step) and the Adam step
+        (_LoopState.adam_step). The iteration counter and Adam moments live in device memory."""
+        inp_data, out_data = inp_data.contiguous(), out_data.contiguous()
+        # an im2col form reads its own unfolded copy of the input cache (a fresh allocation)
+        aligned = out_data.data_ptr() % 16 == 0 and (
+            inp_data.data_ptr() % 16 == 0 or _im2col_ok(module, inp_data.shape, inp_data.element_size()))
+        plan = plan_loop(module, inp_data.shape, inp_data.dtype, out_data.shape, out_data.dtype, act_func, aligned)
+        w, dev, d, o, alpha = _loop_setup(module, delta, offset, ch_axis, alpha_init)
         sq = _BoundSoftQuant(w, alpha, d, o, bitwidth, ch_axis, round_loss_out)
-        iters, n = opt_params.num_iterations, inp_data.shape[0]
-        nb = min(n, BATCH_SIZE)
-        idx_all, draw, staged = AdaroundOptimizer._drawer(generator, n, iters, dev)
-        chunk = 500
-        draw(0, min(chunk, iters))
-        rb_all = AdaroundOptimizer._reg_beta_all(opt_params, iters, dev)
-        im2col = (_GEMM_LAYERS and _LOOP_FORM != "autograd" and out_data.dim() == 4
-                  and out_data.dtype == torch.float32 and _act_code(act_func) is not None
-                  and _im2col_ok(module, inp_data))
-        if im2col:
-            # the cached inputs unfolded once ([N, C_in k k, OH OW]): each iteration's batch is then
-            # a pointwise GEMM problem, gathered by rows like any other cache
-            inp_data = torch.nn.functional.unfold(inp_data, module.kernel_size, module.dilation, module.padding,
-                                                  module.stride)
-        inp_data = inp_data.contiguous()
-        out_data = out_data.contiguous()
-        inp = torch.empty((nb,) + tuple(inp_data.shape[1:]), dtype=inp_data.dtype, device=dev)
-        target = torch.empty((nb,) + tuple(out_data.shape[1:]), dtype=out_data.dtype, device=dev)
-        row_in, row_out = inp[0].numel(), target[0].numel()
-        exp_avg, exp_avg_sq = torch.zeros_like(alpha), torch.zeros_like(alpha)
-        counters = torch.zeros(2, dtype=torch.long, device=dev)   # [it_cur, it_next]
-        wq = torch.empty_like(sq.w).requires_grad_(True)
-        lib = _native.load()
-        P = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
-        it_cur, it_next = ctypes.c_void_p(counters.data_ptr()), ctypes.c_void_p(counters.data_ptr() + 8)
-        adam = (ctypes.c_double(1e-3), ctypes.c_double(0.9), ctypes.c_double(0.999), ctypes.c_double(1e-8))
-        # Adam's bias corrections for every step of the loop, computed once (the same device
-        # arithmetic the step would run per wave: same bits)
-        bias_corr = torch.empty(iters, 2, dtype=torch.float32, device=dev)
-        _native.check(lib.aimet_adaround_adam_bias_corrections(adam[1], adam[2], iters, P(bias_corr),
-                                                               ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        loss_ptr = P(round_loss_out) if round_loss_out is not None else None
-        code = _act_code(act_func)
-        out_shape = tuple(out_data.shape[1:])
-        # the fused reconstruction gradient reads the fp target in place (no gathered copy) when it
-        # has a fused form: [N, C, ...] outputs, ReLU / ReLU6 / no activation
-        indexed = code is not None and out_data.dim() >= 2 and out_data.dtype == torch.float32
-        C_out = out_shape[0] if out_data.dim() >= 2 else 1
-        hw = row_out // C_out if indexed else 1
-        bias = module.bias.detach().contiguous() if module.bias is not None else None
-        mode = "autograd"
-        if im2col and indexed:
-            mode = "im2col"
-        elif indexed and depthwise_spec(module) is not None and inp.dim() == 4:
-            mode = "dw"
-        elif indexed and _GEMM_LAYERS and _is_pointwise(module) and inp.dim() == 4:
-            mode = "pointwise"
-        elif indexed and _GEMM_LAYERS and isinstance(module, torch.nn.Linear) and inp.dim() == 2:
-            mode = "linear"
-        q_buf = torch.empty((nb,) + out_shape, dtype=torch.float32, device=dev)
-        g_buf = torch.empty_like(q_buf)
-        dw_slices = 0
-        if mode == "dw":
-            # depthwise layers: native forward + weight gradient, no autograd (aimet_dwconv2d_*)
-            K, stride, pad, dil = depthwise_spec(module)
-            Nb, C, H, W = inp.shape
-            gw_dw = torch.empty_like(sq.w)
-            ws_n = ctypes.c_int64()
-            _native.check(lib.aimet_dwconv2d_grad_weight_workspace(Nb, C, out_shape[1], out_shape[2], K,
-                                                                   ctypes.byref(ws_n)))
-            ws = torch.empty(ws_n.value, dtype=torch.float32, device=dev)
-            dims = (Nb, C, H, W, out_shape[1], out_shape[2], K, stride, pad, dil)
-            if _DW_FOLD_ADAM and _DW_FUSED and sq.shape[0] * sq.shape[1] * sq.shape[2] == C * K * K:
-                sl = ctypes.c_int64()
-                _native.check(lib.aimet_adaround_dw_step_slices(P(out_data), Nb, C, out_shape[1], out_shape[2], K,
-                                                                stride, dil, ctypes.byref(sl)))
-                dw_slices = sl.value
-        pbias = P(bias) if bias is not None else None
-        pw_dims, cm, pw_slices = None, None, None
-        if mode in ("pointwise", "im2col") and _PW_FUSED != "0" and _LOOP_FORM != "autograd":
-            cin, cout, hw_in = inp_data.shape[1], C_out, inp_data[0, 0].numel()
-            wanted = _PW_FUSED == "all" or (hw >= 28 * 28 and (not (cin > cout and hw < 56 * 56) or
-                                                              (cin >= 32 and _pw_step_uses_mfma(cin, cout))))
-            if (wanted and cin <= 192 and hw_in == hw and hw % 4 == 0
-                    and inp_data.data_ptr() % 16 == 0 and out_data.data_ptr() % 16 == 0 and wq.is_contiguous()):
-                pw_dims = (nb, cin, cout, hw)
-                gw_pw = torch.empty_like(sq.w)
-                ws_n = ctypes.c_int64()
-                _native.check(lib.aimet_adaround_pw_step_workspace(*pw_dims, ctypes.byref(ws_n)))
-                ws_pw = torch.empty(ws_n.value, dtype=torch.float32, device=dev)
-                if _DW_FOLD_ADAM and sq.w.numel() == cin * cout:
-                    # the step's slices added by the Adam step (pw_fold_final's sum, one launch fewer)
-                    off, nsl = ctypes.c_int64(), ctypes.c_int64()
-                    _native.check(lib.aimet_adaround_pw_step_slices(*pw_dims, ctypes.byref(off), ctypes.byref(nsl)))
-                    pw_slices = (off.value, nsl.value)
-        if (mode in ("pointwise", "im2col") and pw_dims is None and _PW_CM and hw <= 14 * 14
-                and inp_data[0].numel() % hw == 0):
-            cin_cm = inp_data[0].numel() // hw
-            x_cm = torch.empty((cin_cm, nb * hw), dtype=torch.float32, device=dev)
-            q_cm = torch.empty((C_out, nb * hw), dtype=torch.float32, device=dev)
-            cm = (cin_cm, x_cm, q_cm, torch.empty_like(q_cm))
-
-        def recon(q, with_bias, s):
-            _native.check(lib.aimet_adaround_recon_grad_indexed(P(q), P(out_data), P(idx_all), it_cur, P(g_buf), nb,
-                                                                C_out, hw, pbias if with_bias else None, code, s))
-
-        def adam_step(gw, s):
-            # the Adam step also writes the next iteration's soft-quantized weight into wq (it reads
-            # W and the new alpha anyway): no separate forward launch per iteration
-            _native.check(lib.aimet_adaround_backward_adam_parts(sq.pw, sq.pa, P(gw), 1, 0, P(exp_avg), P(exp_avg_sq),
-                                                                 *sq.shape, sq.pd, sq.po, sq.bw, P(rb_all), it_next,
-                                                                 it_cur, *adam, loss_ptr, P(wq), P(bias_corr), s))
-
-        def soft_weight():   # wq from the current alpha (before the first iteration)
-            s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _native.check(sq.fwd(sq.pw, sq.pa, P(wq), *sq.shape, sq.pd, sq.po, sq.bw, 1, s))
-
-        def step():
-            s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            if mode == "dw" and _DW_FUSED:
-                # the batch read in place from the caches, q and g never stored; it_next moves here
-                if dw_slices:
-                    # the per-channel slices folded by the Adam step (one launch fewer; the same sum)
-                    _native.check(lib.aimet_adaround_dw_step(P(inp_data), P(out_data), P(idx_all), it_cur, it_next,
-                                                             P(wq), pbias, None, P(ws), *dims, code, s))
-                    _native.check(lib.aimet_adaround_backward_adam_parts(
-                        sq.pw, sq.pa, P(ws), dw_slices, dims[6] * dims[6], P(exp_avg), P(exp_avg_sq), *sq.shape,
-                        sq.pd, sq.po, sq.bw, P(rb_all), it_next, it_cur, *adam, loss_ptr, P(wq),
-                        P(bias_corr), s))
-                    return
-                _native.check(lib.aimet_adaround_dw_step(P(inp_data), P(out_data), P(idx_all), it_cur, it_next,
-                                                         P(wq), pbias, P(gw_dw), P(ws), *dims, code, s))
-                adam_step(gw_dw, s)
-                return
-            if mode in ("pointwise", "im2col") and pw_dims is not None:
-                # 1x1 / unfolded stem with few channels: one pass, the batch read in place
-                if pw_slices:
-                    _native.check(lib.aimet_adaround_pw_step(P(inp_data), P(out_data), P(idx_all), it_cur, it_next,
-                                                             P(wq), pbias, None, P(ws_pw), *pw_dims, code, s))
-                    _native.check(lib.aimet_adaround_backward_adam_parts(
-                        sq.pw, sq.pa, ctypes.c_void_p(ws_pw.data_ptr() + 4 * pw_slices[0]), pw_slices[1],
-                        sq.w.numel(), P(exp_avg), P(exp_avg_sq), *sq.shape, sq.pd, sq.po, sq.bw, P(rb_all), it_next,
-                        it_cur, *adam, loss_ptr, P(wq), P(bias_corr), s))
-                    return
-                _native.check(lib.aimet_adaround_pw_step(P(inp_data), P(out_data), P(idx_all), it_cur, it_next,
-                                                         P(wq), pbias, P(gw_pw), P(ws_pw), *pw_dims, code, s))
-                adam_step(gw_pw, s)
-                return
-            if mode in ("pointwise", "im2col") and cm is not None:
-                # channel-major batch: one GEMM per direction over all nb * hw positions
-                cin_cm, x_cm, q_cm, g_cm = cm
-                _native.check(lib.aimet_adaround_gather_cm(P(inp_data), P(x_cm), P(idx_all), it_cur, it_next, nb,
-                                                           cin_cm, hw, s))
-                w2 = wq.detach().view(wq.shape[0], -1)
-                torch.mm(w2, x_cm, out=q_cm)
-                _native.check(lib.aimet_adaround_recon_grad_indexed_cm(P(q_cm), P(out_data), P(idx_all), it_cur,
-                                                                       P(g_cm), nb, C_out, hw, pbias, code, s))
-                adam_step(torch.mm(g_cm, x_cm.t()).view_as(wq), s)
-                return
-            _native.check(lib.aimet_adaround_gather(P(inp_data), P(out_data), P(inp),
-                                                    None if indexed else P(target), P(idx_all), it_cur, it_next, nb,
-                                                    row_in, row_out, s))
-            if mode == "dw":
-                _native.check(lib.aimet_dwconv2d_forward(P(inp), P(wq), pbias, P(q_buf), *dims, s))
-                recon(q_buf, False, s)
-                _native.check(lib.aimet_dwconv2d_grad_weight(P(inp), P(g_buf), P(gw_dw), P(ws), *dims, s))
-                adam_step(gw_dw, s)
-                return
-            if mode in ("pointwise", "im2col"):
-                # 1x1 convolution (or the unfolded stem) as one batched GEMM per direction
-                # (hipBLASLt, no NCHW<->NHWC transposes): q[n] = Wq @ x[n]; the bias is added inside
-                # the reconstruction kernel
-                x3 = inp.view(nb, inp.shape[1], -1)
-                w2 = wq.detach().view(wq.shape[0], -1)
-                torch.matmul(w2, x3, out=q_buf.view(nb, w2.shape[0], -1))
-                recon(q_buf, True, s)
-                g3 = g_buf.view(nb, w2.shape[0], -1)
-                if _PW_GRAD == "mm" or (_PW_GRAD == "auto" and g3.shape[2] <= 64):
-                    # one GEMM over (n, hw): [C_out, nb * hw] @ [nb * hw, C_in] from channel-major copies
-                    gw = torch.mm(g3.transpose(0, 1).reshape(w2.shape[0], -1),
-                                  x3.transpose(0, 1).reshape(w2.shape[1], -1).t())
-                else:
-                    gw = torch.matmul(g3, x3.transpose(1, 2)).sum(0)
-                adam_step(gw.contiguous().view_as(wq), s)
-                return
-            if mode == "linear":
-                torch.mm(inp, wq.detach().t(), out=q_buf)
-                recon(q_buf, True, s)
-                adam_step(torch.mm(g_buf.t(), inp), s)
-                return
-            q_out = layer_forward(module, inp, wq)
-            if indexed:
-                recon(q_out, False, s)
-                (gw,) = torch.autograd.grad(q_out, wq, grad_outputs=g_buf)
-            else:
-                qa, ta = (act_func(q_out), act_func(target)) if act_func is not None else (q_out, target)
-                (gw,) = torch.autograd.grad(recon_loss(qa, ta), wq)
-            adam_step(gw if gw.is_contiguous() else gw.contiguous(), s)
-
-        alpha0 = alpha.detach().clone()
-        loss0 = round_loss_out.clone() if round_loss_out is not None else None
-
-        def restart():   # back to iteration 0
-            with torch.no_grad():
-                alpha.copy_(alpha0)
-                exp_avg.zero_()
-                exp_avg_sq.zero_()
-                counters.zero_()
-                if round_loss_out is not None:
-                    round_loss_out.copy_(loss0)
-            soft_weight()
-
-        def capture(m, k=1):
-            nonlocal mode
-            mode = m
-            # warm-up on a side stream (library handles, allocator, autograd), then capture
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side), torch.enable_grad():
-                soft_weight()
-                for _ in range(min(2, iters)):
-                    step()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            restart()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g), torch.enable_grad():
-                for _ in range(k):   # k consecutive iterations (the counters advance on the device)
-                    step()
-            return g
-
-        # layers with two forms (GEMM or MIOpen convolution through autograd): the form is fixed by
-        # _LOOP_FORM (deterministic results); the convolution form only when the GEMM form cannot be
-        # captured
-        two_forms = mode in ("pointwise", "linear")
-        if two_forms and _LOOP_FORM == "autograd":
-            mode = "autograd"
-        candidates = [mode] + (["autograd"] if two_forms and mode != "autograd" else [])
-        graph = None
-        for m in candidates:
-            try:
-                graph = capture(m)
-            except RuntimeError:
-                if m == candidates[0] and len(candidates) > 1:
-                    continue   # the GEMM form could not be captured: the convolution form
-                raise
-            mode = m
-            break
-        AdaroundOptimizer.last_loop_form = mode + ("_fused" if mode in ("pointwise", "im2col") and pw_dims else
-                                                   "_cm" if mode in ("pointwise", "im2col") and cm else "")
-        k = min(_GRAPH_ITERS, chunk)
-        graph_k = None
-        if k > 1 and iters >= k:
-            try:
-                graph_k = capture(mode, k)
-            except RuntimeError:
-                # k iterations could not be captured (graph-pool memory, an autograd form): the
-                # one-iteration graph runs them, the same results (ADVICE r04)
-                graph_k = None
-            restart()
-        for a in range(0, iters, chunk):
-            b = min(a + chunk, iters)
-            if b < iters:
-                draw(b, min(b + chunk, iters))
-            i = a
-            while graph_k is not None and i + k <= b:
-                graph_k.replay()
-                i += k
-            for _ in range(i, b):
-                graph.replay()
-        torch.cuda.current_stream(dev).synchronize()
-        del staged
+        iters = opt_params.num_iterations
+        idx_all, draw = AdaroundOptimizer._drawer(generator, inp_data.shape[0], iters, dev)
+        st = _LoopState(plan, module, inp_data, out_data, sq, iters, idx_all,
+                        AdaroundOptimizer._reg_beta_all(opt_params, iters, dev), act_func, round_loss_out)
+        AdaroundOptimizer.last_loop_form = _run_captured(st, draw)
         return _finish_alpha(alpha, alpha_init)
 
     @staticmethod
@@ -825,41 +890,12 @@ class AdaroundOptimizer:
             return AdaroundOptimizer._optimize_fused_graph(module, inp_data, out_data, delta, offset, bitwidth,
                                                            ch_axis, opt_params, act_func, generator, round_loss_out,
                                                            alpha_init)
-        w = module.weight.detach()
-        dev = w.device
-        shape = [1] * w.dim()
-        shape[ch_axis] = -1
-        d = torch.as_tensor(delta, dtype=torch.float32, device=dev).reshape(-1)
-        o = torch.as_tensor(offset, dtype=torch.float32, device=dev).reshape(-1)
-        alpha = _starting_alpha(w, d, shape, alpha_init)
-        lr = 1e-3 * world
-        try:
-            optimizer = torch.optim.Adam([alpha], lr=lr, capturable=True, fused=True)
-        except (RuntimeError, TypeError):
-            optimizer = torch.optim.Adam([alpha], lr=lr, capturable=True)
+        w, dev, d, o, alpha = _loop_setup(module, delta, offset, ch_axis, alpha_init)
+        optimizer = _torch_adam(alpha, world, capturable=True)
         sq = _BoundSoftQuant(w, alpha, d, o, bitwidth, ch_axis, round_loss_out)
-        iters, n = opt_params.num_iterations // world, inp_data.shape[0]
-        warm = opt_params.num_iterations * opt_params.warm_start
-        # the eager loop's draws, in its order: drawn on the host chunk by chunk while the GPU replays
-        # the previous chunk (stream-ordered pinned copies into idx_all)
-        nb = min(n, BATCH_SIZE)
-        idx_all = torch.empty((iters, nb), dtype=torch.long, device=dev)
-        chunk = 500
-        staged = []
-
-        def draw(a, b):
-            h = torch.stack([torch.randperm(n, generator=generator)[:BATCH_SIZE] for _ in range(a, b)]).pin_memory()
-            idx_all[a:b].copy_(h, non_blocking=True)
-            staged.append(h)   # alive until the copies have run (synchronised below)
-
-        draw(0, min(chunk, iters))
-        # {reg, beta, beta - 1} of every iteration, formed in double as the reference's python / ATen
-        # pow_backward do, then stored as float32 (the kernel's arithmetic type)
-        rb_all = torch.tensor([(0.0, 0.0, 0.0) if it < warm else
-                               (lambda b: (opt_params.reg_param, b, b - 1.0))(
-                                   compute_beta(opt_params.num_iterations, it, opt_params.beta_range,
-                                                opt_params.warm_start))
-                               for it in range(max(iters, 1))], dtype=torch.float64).to(torch.float32).to(dev)
+        iters = opt_params.num_iterations // world
+        idx_all, draw = AdaroundOptimizer._drawer(generator, inp_data.shape[0], iters, dev)
+        rb_all = AdaroundOptimizer._reg_beta_all(opt_params, iters, dev)
         it_buf = torch.zeros(1, dtype=torch.long, device=dev)
         alpha.grad = torch.zeros_like(alpha)
 
@@ -907,7 +943,7 @@ class AdaroundOptimizer:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 step()
-            replay = graph.replay
+            replay_one = graph.replay
         else:
             # the collective between two graphs (any backend; gloo stages through the host)
             g_grad, g_upd = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -916,17 +952,15 @@ class AdaroundOptimizer:
             with torch.cuda.graph(g_upd):
                 update_step()
 
-            def replay():
+            def replay_one():
                 g_grad.replay()
                 _reduce_grad(alpha.grad, world, group, divide=False)
                 g_upd.replay()
-        for a in range(0, iters, chunk):
-            b = min(a + chunk, iters)
-            if b < iters:
-                draw(b, min(b + chunk, iters))
-            for _ in range(a, b):
-                replay()
-        torch.cuda.current_stream(dev).synchronize()
+
+        def replay(count):
+            for _ in range(count):
+                replay_one()
+        _replay_chunks(iters, draw, replay, dev)
         sq.reg_beta = None
         return _finish_alpha(alpha, alpha_init)
 

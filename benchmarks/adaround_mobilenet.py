@@ -8,14 +8,17 @@ warm start 0.2, ReLU6 applied to both outputs when the layer feeds one); then wr
 hard-rounded weight. Weight encodings: 8-bit symmetric per-tensor TF-Enhanced (AIMET's AdaRound
 default) from the device analyzers.
 
-Reported (one JSON line): total AdaRound wall-clock, mean ms per iteration, and per layer its ms
-per iteration and the loop form that ran it (dw: native depthwise kernels; pointwise / linear:
-direct GEMMs; autograd: MIOpen through autograd -- layers with two forms time both at capture and
-keep the faster); with --reference-iters the same loop using the reference's torch-op soft
+Reported (one JSON line): total AdaRound wall-clock, mean ms per iteration, a SHA-256 over the
+adarounded weights of all layers, and per layer its ms per iteration and the loop form that ran it
+(adaround_optimizer.plan_loop, a fixed rule by layer shape -- dw: native depthwise kernels;
+pointwise / linear: direct GEMMs, im2col: the same on an unfolded stem; _cm: the GEMMs over
+channel-major batches, _fused: the one-pass 1x1 step; autograd: MIOpen through autograd);
+with --reference-iters the same loop using the reference's torch-op soft
 quantization + rounding loss (oracle/torch_ref.py) for comparison. The per-kernel split of the
 loop comes from rocprofv3 (tools/studies/ada_trace_summary.py), not from host-timed launches.
 """
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -84,6 +87,7 @@ def main():
     loss_buf = torch.zeros(1, device=dev)
     t_opt = t_cache = t_ref = 0.0
     per_layer = []
+    sha = hashlib.sha256()
     for name in names:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -114,6 +118,7 @@ def main():
                           AdaroundOptimizer.last_loop_form])
         with torch.no_grad():
             m.weight.copy_(AdaroundOptimizer.hard_rounded_weight(m, alpha, d, o, 8))
+        sha.update(m.weight.detach().cpu().numpy().tobytes())
         if args.reference_iters:
             from oracle import torch_ref as T
             a_ref = init_alpha(w, d)
@@ -149,6 +154,7 @@ def main():
         "miopen_find": bool(args.miopen_find),
         "rounding_loss_pow": "exact (torch's CPU pow, bit for bit)" if args.exact_pow else "table-driven f32 (within 1 ulp of torch's)",
         "weights_elems": sum(int(torch.Size(p[1]).numel()) for p in per_layer),
+        "weights_sha256": sha.hexdigest(),
         "kernel_split": "per-kernel time of the loop: rocprofv3 --kernel-trace + tools/studies/ada_trace_summary.py "
                         "(profiles/r02/adaround_loop_kernels_*.csv)",
         "data": "synthetic U(0,1) images (seed 7), random-init MobileNet-v2 with folded BN (seed 0)",

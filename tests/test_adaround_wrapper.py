@@ -186,25 +186,107 @@ def test_activation_sampler_concatenates_batches():
         assert torch.equal(out, torch.cat([orig(d) for d in data]))
 
 
+def _plan(m, shape_in, act=None, aligned=True):
+    """plan_loop's form for `m` on float32 caches of shape_in and of the output shape it gives."""
+    from aimet_amd.adaround_optimizer import plan_loop
+    with torch.no_grad():
+        shape_out = (shape_in[0],) + tuple(m(torch.zeros((1,) + tuple(shape_in[1:]))).shape[1:])
+    return plan_loop(m, tuple(shape_in), torch.float32, shape_out, torch.float32, act, aligned)
+
+
+def test_adaround_plan_mobilenet_v2_forms(golden_dir):
+    """The planner on the 53 conv / linear layers of MobileNet-v2 at 224 x 224 with 1024 cached
+    samples gives the forms the 10k-iteration benchmark recorded per layer
+    (tests/golden/adaround_loop_forms.json: names and forms of profiles/r05/adaround_mobilenet_10k.json)."""
+    import json
+    from workloads.mobilenet_v2 import mobilenet_v2
+    net = mobilenet_v2(seed=0)
+    layers = [(n, m) for n, m in net.named_modules() if isinstance(m, (nn.Conv2d, nn.Linear))]
+    follow = {}   # the ReLU6 after a layer, as benchmarks/adaround_mobilenet.py finds it
+    for parent in net.modules():
+        kids = list(parent.children())
+        follow.update({a: b for a, b in zip(kids, kids[1:]) if isinstance(b, nn.ReLU6)})
+    shapes = {}
+    hooks = [m.register_forward_hook(lambda mod, i, o: shapes.__setitem__(mod, tuple(i[0].shape))) for _, m in layers]
+    with torch.no_grad():
+        net(torch.zeros(1, 3, 224, 224))
+    for h in hooks:
+        h.remove()
+    got = [[n, _plan(m, (1024,) + shapes[m][1:], follow.get(m)).form] for n, m in layers]
+    with open(os.path.join(golden_dir, "adaround_loop_forms.json")) as f:
+        assert got == json.load(f)
+
+
+def _layer(kind, *a):
+    """(module, input cache shape with 64 samples) of a test layer, built when the test runs."""
+    if kind == "stem":      # 3 -> a[0] channels, k3 s2, from a[1] x a[1] input
+        return nn.Conv2d(3, a[0], 3, stride=2, padding=1), (64, 3, a[1], a[1])
+    if kind == "pw":        # a[0] -> a[1] channels at a[2] x a[2]
+        return nn.Conv2d(a[0], a[1], 1), (64, a[0], a[2], a[2])
+    if kind == "dw":        # depthwise, kernel a[0]
+        return nn.Conv2d(16, 16, a[0], padding=a[0] // 2, groups=16), (64, 16, 14, 14)
+    if kind == "conv3":     # C_in k k = 144 > 64: no im2col form
+        return nn.Conv2d(16, 16, 3, padding=1), (64, 16, 14, 14)
+    return nn.Linear(96, 40), (64, 96)
+
+
+@pytest.mark.parametrize("layer,act,aligned,want", [
+    (("pw", 16, 48, 14), nn.ReLU6(), True, "pointwise_cm"),
+    (("pw", 16, 48, 16), nn.ReLU6(), True, "pointwise"),
+    (("pw", 16, 96, 28), nn.ReLU6(), True, "pointwise_fused"),
+    (("pw", 192, 32, 28), nn.ReLU6(), True, "mfma"),            # pointwise_fused exactly when on the matrix cores
+    (("pw", 200, 32, 28), nn.ReLU6(), True, "pointwise"),       # C_in > 192
+    (("pw", 144, 24, 56), nn.ReLU6(), True, "pointwise_fused"),
+    (("pw", 16, 96, 27), nn.ReLU6(), True, "pointwise"),        # hw % 4 != 0
+    (("stem", 16, 28), nn.ReLU6(), True, "im2col_cm"),
+    (("stem", 16, 32), nn.ReLU6(), True, "im2col"),
+    (("stem", 32, 64), nn.ReLU6(), True, "im2col_fused"),
+    (("conv3",), nn.ReLU6(), True, "autograd"),
+    (("dw", 3), nn.ReLU6(), True, "dw"),
+    (("dw", 5), nn.ReLU6(), True, "dw"),
+    (("dw", 7), nn.ReLU6(), True, "autograd"),
+    (("linear",), nn.ReLU6(), True, "linear"),
+    (("pw", 16, 48, 14), nn.Hardswish(), True, "autograd"),     # no fused reconstruction gradient
+    (("pw", 16, 96, 28), nn.ReLU6(), False, "pointwise"),       # a cache off the 16-byte boundary
+])
+def test_adaround_plan_boundaries(layer, act, aligned, want):
+    """plan_loop at the edges of its rules (the channel-major form up to 14 x 14, the one-pass
+    step from 28 x 28 with C_in <= 192 and hw % 4 == 0 on aligned caches, im2col up to
+    C_in k k = 64, native depthwise for K in {3, 5}), on a machine without a GPU."""
+    from aimet_amd.adaround_optimizer import _pw_step_uses_mfma
+    m, shape_in = _layer(*layer)
+    if want == "mfma":
+        want = "pointwise_fused" if _pw_step_uses_mfma(m.in_channels, m.out_channels) else "pointwise"
+    plan = _plan(m, shape_in, act, aligned)
+    assert plan.form == want
+    assert plan.fallback == ("autograd" if want.startswith("pointwise") or want == "linear" else None)
+    assert plan.indexed == (not isinstance(act, nn.Hardswish))
+
+
+_LOOP_KINDS = {   # kind: (layer, activation, the loop form it runs)
+    "stem": (("stem", 16, 32), nn.ReLU6(), "im2col"),
+    "stem_cm": (("stem", 16, 28), nn.ReLU6(), "im2col_cm"),
+    "dw": (("dw", 3), nn.ReLU6(), "dw"),
+    "pointwise": (("pw", 16, 48, 14), nn.ReLU6(), "pointwise_cm"),
+    "pointwise_wide": (("pw", 576, 96, 14), nn.ReLU6(), "pointwise_cm"),   # MobileNet-v2's 14x14 projection
+    "linear": (("linear",), nn.ReLU6(), "linear"),
+    "autograd": (("conv3",), nn.ReLU6(), "autograd"),                     # the indexed reconstruction gradient
+    "autograd_hardswish": (("pw", 16, 48, 14), nn.Hardswish(), "autograd"),   # torch ops on a gathered target
+}
+
+
 @pytest.mark.gpu
 @gpu
-@pytest.mark.parametrize("kind", ["stem", "dw", "pointwise", "pointwise_wide", "linear"])
+@pytest.mark.parametrize("kind", list(_LOOP_KINDS))
 def test_adaround_loop_deterministic(kind):
     """Two runs of the fused loop with one seed give bit-identical alpha, for every loop form
     (MIOpen through autograd, native depthwise, GEMM pointwise / linear): the form is a fixed rule
-    and the convolutions deterministic."""
+    and the convolutions deterministic. The form that ran is the planner's."""
     from aimet_amd.adaround_optimizer import AdaroundHyperParameters, AdaroundOptimizer
     torch.manual_seed(3)
-    if kind == "stem":
-        m, shape_in = nn.Conv2d(3, 16, 3, stride=2, padding=1), (64, 3, 32, 32)
-    elif kind == "dw":
-        m, shape_in = nn.Conv2d(16, 16, 3, padding=1, groups=16), (64, 16, 14, 14)
-    elif kind == "pointwise":
-        m, shape_in = nn.Conv2d(16, 48, 1), (64, 16, 14, 14)
-    elif kind == "pointwise_wide":   # MobileNet-v2's 14x14 projection: the channel-major GEMM form
-        m, shape_in = nn.Conv2d(576, 96, 1), (64, 576, 14, 14)
-    else:
-        m, shape_in = nn.Linear(96, 40), (64, 96)
+    layer, act, form = _LOOP_KINDS[kind]
+    m, shape_in = _layer(*layer)
+    assert _plan(m, shape_in, act).form == form
     m = m.to(DEV)
     inp = torch.rand(shape_in, device=DEV)
     with torch.no_grad():
@@ -212,9 +294,10 @@ def test_adaround_loop_deterministic(kind):
     d = (m.weight.detach().abs().max() / 127).reshape(1)
     o = torch.full((1,), -128.0, device=DEV)
     p = AdaroundHyperParameters(num_iterations=300, warm_start=0.2)
-    a = [AdaroundOptimizer.optimize_rounding(m, inp, out, d, o, 8, 0, p, nn.ReLU6(),
+    a = [AdaroundOptimizer.optimize_rounding(m, inp, out, d, o, 8, 0, p, act,
                                              torch.Generator().manual_seed(5)).detach().clone() for _ in range(2)]
     assert torch.equal(a[0], a[1]), AdaroundOptimizer.last_loop_form
+    assert AdaroundOptimizer.last_loop_form == form
 
 
 def _loop_problem(kind, seed=3):
@@ -240,7 +323,7 @@ def _loop_problem(kind, seed=3):
 @gpu
 @pytest.mark.parametrize("kind", ["stem", "dw", "pointwise_wide", "linear"])
 def test_adaround_multi_iteration_graph_equals_one_per_graph(monkeypatch, kind):
-    """k iterations captured in one HIP graph (AIMET_ADA_GRAPH_ITERS; the counters and the batch
+    """k iterations captured in one HIP graph (adaround_optimizer._GRAPH_ITERS; the counters and the batch
     table live on the device) give the alpha of one iteration per graph, bit for bit, also when k
     does not divide the iteration count (the rest replays the one-iteration graph)."""
     import aimet_amd.adaround_optimizer as ao
