@@ -9,7 +9,7 @@ import torch
 from torch import nn
 
 from aimet_amd import _native
-from aimet_amd._native import DfqBnFoldJobC, DfqWeightC
+from aimet_amd._native import BnreFoldScaleJobC, DfqBnFoldJobC, DfqWeightC
 
 _TRANSPOSED = (nn.ConvTranspose1d, nn.ConvTranspose2d, nn.ConvTranspose3d)
 
@@ -93,19 +93,40 @@ def bn_fold_launch(stage: Stage, jobs: List[dict]):
     if not jobs:
         return
     table = (DfqBnFoldJobC * len(jobs))()
+    keep = [_fill_bn_fold_job(stage, slot, j) for slot, j in zip(table, jobs)]
+    _run_bn_fold("aimet_dfq_bn_fold", stage, table, jobs)
+    del keep
+
+
+def bn_fold_scale_launch(stage: Stage, jobs: List[dict]):
+    """One aimet_bnre_fold_scale launch: backward folds as bn_fold_launch takes them, each with
+    enc_min / enc_max (device float32 vectors of cout elements, updated in place)."""
+    if not jobs:
+        return
+    table = (BnreFoldScaleJobC * len(jobs))()
     keep = []
     for slot, j in zip(table, jobs):
-        bn = j["bn"]
-        vecs = [stage.dev(bn.weight), stage.dev(bn.bias), stage.dev(bn.running_mean), stage.dev(bn.running_var)]
-        keep.append(vecs)
-        slot.w = weight_desc(j["module"], j["weight"])
-        slot.bias = j["bias"].data_ptr()
-        slot.gamma, slot.beta, slot.mean, slot.var = (v.data_ptr() for v in vecs)
-        slot.eps = float(bn.eps)
-        slot.forward = 1 if j["forward"] else 0
+        keep.append(_fill_bn_fold_job(stage, slot.fold, j))
+        slot.enc_min, slot.enc_max = j["enc_min"].data_ptr(), j["enc_max"].data_ptr()
+    _run_bn_fold("aimet_bnre_fold_scale", stage, table, jobs)
+    del keep
+
+
+def _fill_bn_fold_job(stage: Stage, slot, j: dict):
+    bn = j["bn"]
+    vecs = [stage.dev(bn.weight), stage.dev(bn.bias), stage.dev(bn.running_mean), stage.dev(bn.running_var)]
+    slot.w = weight_desc(j["module"], j["weight"])
+    slot.bias = j["bias"].data_ptr()
+    slot.gamma, slot.beta, slot.mean, slot.var = (v.data_ptr() for v in vecs)
+    slot.eps = float(bn.eps)
+    slot.forward = 1 if j["forward"] else 0
+    return vecs   # alive until the launch
+
+
+def _run_bn_fold(entry: str, stage: Stage, table, jobs: List[dict]):
     status = stage.new(len(jobs), torch.int32)
     with torch.cuda.device(stage.device):
-        _native.call("aimet_dfq_bn_fold", table, len(jobs), ptr(status), ctypes.c_void_p(stage.stream))
+        _native.call(entry, table, len(jobs), ptr(status), ctypes.c_void_p(stage.stream))
     bad = status.cpu().nonzero().flatten().tolist()
     if bad:
         raise ValueError("batch norm fold: sqrt(running_var + eps) is zero in %s" %
@@ -118,17 +139,23 @@ def bn_fold_launch(stage: Stage, jobs: List[dict]):
 class TracedGraph:
     """The call_module nodes of torch.fx.symbolic_trace(model), with the modules they call."""
 
-    def __init__(self, model: nn.Module):
+    def __init__(self, model: nn.Module, is_leaf=None):
+        """is_leaf: modules m with is_leaf(m) are call_module nodes and not traced into (besides the
+        torch.nn modules fx always keeps whole); default: fx's own rule."""
         import torch.fx
+
+        class Tracer(torch.fx.Tracer):
+            def is_leaf_module(self, m, module_qualified_name):
+                return (is_leaf is not None and is_leaf(m)) or super().is_leaf_module(m, module_qualified_name)
         try:
-            traced = torch.fx.symbolic_trace(model)
+            graph = Tracer().trace(model)
         except Exception as e:  # fx raises several kinds of error for control flow on tensors
             raise RuntimeError(
                 "aimet_amd: torch.fx cannot trace %s (%s: %s), so batch norms and cross-layer-scaling sets cannot "
                 "be found automatically. Give them explicitly: fold_given_batch_norms(model, layer_pairs) and "
                 "CrossLayerScaling.scale_cls_sets(cls_sets) / HighBiasFold.bias_fold(...) need no graph."
                 % (type(model).__name__, type(e).__name__, e)) from e
-        self.nodes = list(traced.graph.nodes)
+        self.nodes = list(graph.nodes)
         self.module_of: Dict[object, nn.Module] = {}
         self.calls: Dict[nn.Module, int] = {}
         for n in self.nodes:

@@ -92,6 +92,17 @@ class BcAnalyticalJobC(ctypes.Structure):
                 ("beta", ctypes.c_void_p), ("activation", ctypes.c_int32)]
 
 
+class BnreFinishJobC(ctypes.Structure):
+    """aimet_bnre_finish_job."""
+    _fields_ = [("sum_mean", ctypes.c_void_p), ("sum_var", ctypes.c_void_p), ("running_mean", ctypes.c_void_p),
+                ("running_var", ctypes.c_void_p), ("C", ctypes.c_int64), ("count", ctypes.c_double)]
+
+
+class BnreFoldScaleJobC(ctypes.Structure):
+    """aimet_bnre_fold_scale_job."""
+    _fields_ = [("fold", DfqBnFoldJobC), ("enc_min", ctypes.c_void_p), ("enc_max", ctypes.c_void_p)]
+
+
 # name -> argtypes (restype is int status unless listed in _RESTYPES)
 _PROTOTYPES = {
     "aimet_last_error": [],
@@ -243,6 +254,11 @@ _PROTOTYPES = {
     "aimet_bc_launch_count": [_i64p, _int],
     "aimet_qa_sq_err": [_vp, _vp, _i64, _int, ctypes.c_double, _vp, _vp],
     "aimet_qa_launch_count": [_i64p, _int],
+    "aimet_bnre_forward": [_vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp],
+    "aimet_bnre_forward_form": [_int, ctypes.POINTER(_int)],
+    "aimet_bnre_finish": [ctypes.POINTER(BnreFinishJobC), _i64, _vp],
+    "aimet_bnre_fold_scale": [ctypes.POINTER(BnreFoldScaleJobC), _i64, _vp, _vp],
+    "aimet_bnre_launch_count": [_i64p, _int],
 }
 _RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p}
 

@@ -264,6 +264,9 @@ void fold_buffers_release(const FoldBuffers& f, hipStream_t s);
 size_t capture_pool_limit(size_t arena_floats);
 void scratch_free(void* p, hipStream_t s);
 
+// bn_reest.hip: adds to the count aimet_bnre_launch_count reports (the fold to scale lives in dfq.hip)
+void bnre_count_launches(int64_t n);
+
 struct QdqParams
 {
     float min, max, delta, offset;

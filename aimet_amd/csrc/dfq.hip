@@ -199,6 +199,47 @@ struct BnJob
     int64_t cout, cin, k;
 };
 
+// conv -> bn for output channel o, `scale` what was folded in; false, with the status word set and
+// nothing touched, when sqrt(var + eps) is zero
+__device__ __forceinline__ bool bn_fold_backward(const BnJob& j, int64_t o, int32_t* status, float& scale)
+{
+    const float sigma = __builtin_sqrtf(j.var[o] + j.eps);
+    if (sigma == 0.0f)
+    {
+        if (threadIdx.x == 0)
+            status[blockIdx.y] = 1;
+        return false;
+    }
+    scale = j.gamma[o] / sigma;
+    span_scale(j.w.channel(o), scale);
+    if (threadIdx.x == 0)
+        j.bias[o] = j.beta[o] - (j.mean[o] - j.bias[o]) * scale;
+    return true;
+}
+
+// A backward fold that also moves the output channel's learned quantization range onto the scaled
+// weight: (min, max) * c, the ends swapped for a negative c.
+struct BnScaleJob
+{
+    BnJob fold;
+    float *enc_min, *enc_max;
+};
+
+__global__ __launch_bounds__(kDfqBlock) void dfq_bn_fold_scale_kernel(const BnScaleJob* jobs, int32_t* status)
+{
+    const BnScaleJob j = jobs[blockIdx.y];
+    const int64_t o    = blockIdx.x;
+    if (o >= j.fold.cout)
+        return;
+    float c;
+    if (bn_fold_backward(j.fold, o, status, c) && threadIdx.x == 0)
+    {
+        const float lo = j.enc_min[o] * c, hi = j.enc_max[o] * c;
+        j.enc_min[o]   = c >= 0.0f ? lo : hi;
+        j.enc_max[o]   = c >= 0.0f ? hi : lo;
+    }
+}
+
 __global__ __launch_bounds__(kDfqBlock) void dfq_bn_fold_kernel(const BnJob* jobs, int32_t* status)
 {
     __shared__ float lds[kDfqBlock];
@@ -208,17 +249,8 @@ __global__ __launch_bounds__(kDfqBlock) void dfq_bn_fold_kernel(const BnJob* job
         return;
     if (!j.forward)
     {
-        const float sigma = __builtin_sqrtf(j.var[o] + j.eps);
-        if (sigma == 0.0f)
-        {
-            if (threadIdx.x == 0)
-                status[blockIdx.y] = 1;
-            return;
-        }
-        const float scale = j.gamma[o] / sigma;
-        span_scale(j.w.channel(o), scale);
-        if (threadIdx.x == 0)
-            j.bias[o] = j.beta[o] - (j.mean[o] - j.bias[o]) * scale;
+        float scale;
+        bn_fold_backward(j, o, status, scale);
         return;
     }
     // bn -> conv: row o of a [cout][cin][k] weight; a lane owns the input channels i = t, t + 256, ...
@@ -337,6 +369,19 @@ Side in_side(const aimet_dfq_weight& w)
     return Side {w.data, w.in_stride, w.cout, w.k, w.out_stride};
 }
 
+BnJob checked_bn_job(const aimet_dfq_bn_fold_job& j)
+{
+    check_weight(&j.w, "BN fold weight");
+    AIMET_REQUIRE(!j.forward || conv_layout(j.w), "BN fold: forward fold needs a Conv / Linear layout");
+    require_device_ptr(j.bias, "BN fold bias");
+    require_device_ptr(j.gamma, "BN gamma");
+    require_device_ptr(j.beta, "BN beta");
+    require_device_ptr(j.mean, "BN running mean");
+    require_device_ptr(j.var, "BN running var");
+    return BnJob {out_side(j.w), j.bias, j.gamma, j.beta, j.mean, j.var, j.eps, j.forward ? 1 : 0,
+                  j.w.cout,      j.w.cin, j.w.k};
+}
+
 }   // namespace
 }   // namespace aimet_amd
 
@@ -357,17 +402,9 @@ int aimet_dfq_bn_fold(const aimet_dfq_bn_fold_job* jobs, int64_t count, int32_t*
         for (int64_t n = 0; n < count; ++n)
         {
             const aimet_dfq_bn_fold_job& j = jobs[n];
-            check_weight(&j.w, "BN fold weight");
-            AIMET_REQUIRE(!j.forward || conv_layout(j.w), "BN fold: forward fold needs a Conv / Linear layout");
-            require_device_ptr(j.bias, "BN fold bias");
-            require_device_ptr(j.gamma, "BN gamma");
-            require_device_ptr(j.beta, "BN beta");
-            require_device_ptr(j.mean, "BN running mean");
-            require_device_ptr(j.var, "BN running var");
             for (int64_t m = 0; m < n; ++m)
                 AIMET_REQUIRE(jobs[m].w.data != j.w.data, "BN fold: two jobs of one launch on the same weight");
-            table[(size_t) n] = BnJob {out_side(j.w), j.bias, j.gamma, j.beta, j.mean, j.var, j.eps, j.forward ? 1 : 0,
-                                       j.w.cout,      j.w.cin, j.w.k};
+            table[(size_t) n] = checked_bn_job(j);
             max_cout          = std::max(max_cout, j.w.cout);
         }
         hipStream_t s = as_stream(stream);
@@ -377,6 +414,39 @@ int aimet_dfq_bn_fold(const aimet_dfq_bn_fold_job* jobs, int64_t count, int32_t*
         scratch_free(dev, s);
         AIMET_HIP_CHECK(e);
         g_launches.fetch_add(1, std::memory_order_relaxed);
+    });
+}
+
+int aimet_bnre_fold_scale(const aimet_bnre_fold_scale_job* jobs, int64_t count, int32_t* status_dev, void* stream)
+{
+    return guarded([&] {
+        AIMET_REQUIRE(count >= 0 && count <= 65535, "BN fold to scale: 0..65535 jobs per launch");
+        if (count == 0)
+            return;
+        AIMET_REQUIRE(jobs != nullptr, "BN fold to scale: job table is null");
+        require_device_ptr(status_dev, "status");
+        std::vector<BnScaleJob> table((size_t) count);
+        int64_t max_cout = 0;
+        for (int64_t n = 0; n < count; ++n)
+        {
+            const aimet_bnre_fold_scale_job& j = jobs[n];
+            AIMET_REQUIRE(!j.fold.forward, "BN fold to scale: only a BatchNorm behind the layer folds to scale");
+            require_device_ptr(j.enc_min, "BN fold to scale encoding min");
+            require_device_ptr(j.enc_max, "BN fold to scale encoding max");
+            for (int64_t m = 0; m < n; ++m)
+                AIMET_REQUIRE(jobs[m].fold.w.data != j.fold.w.data && jobs[m].enc_min != j.enc_min &&
+                                  jobs[m].enc_max != j.enc_max,
+                              "BN fold to scale: two jobs of one launch on the same weight or range");
+            table[(size_t) n] = BnScaleJob {checked_bn_job(j.fold), j.enc_min, j.enc_max};
+            max_cout          = std::max(max_cout, j.fold.w.cout);
+        }
+        hipStream_t s = as_stream(stream);
+        auto* dev     = static_cast<BnScaleJob*>(upload_async(table.data(), table.size() * sizeof(BnScaleJob), s));
+        dfq_bn_fold_scale_kernel<<<dim3((unsigned) max_cout, (unsigned) count), kDfqBlock, 0, s>>>(dev, status_dev);
+        hipError_t e = hipGetLastError();
+        scratch_free(dev, s);
+        AIMET_HIP_CHECK(e);
+        bnre_count_launches(1);
     });
 }
 

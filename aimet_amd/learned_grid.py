@@ -373,9 +373,10 @@ class LearnedGridTensorQuantizer:
             raise RuntimeError("Encoding can be set only when it is not frozen.")
         self._set_encoding_min_max_parameters(encoding)
 
-    def _compute_updated_encoding(self):
-        """v1/tensor_quantizer.py:775-819: delta / offset from the parameters with the forward's
-        torch float32 arithmetic; asymmetric ranges are moved onto the grid (min = delta * offset)."""
+    def encoding_tensors(self):
+        """(min, max, delta, offset) of the learned encoding(s) as float32 tensors on the parameters'
+        device, one element per channel, or None without parameters: what ``encoding`` reports,
+        before its copy to the host."""
         emin, emax = self._params()
         if emin is None or emax is None:
             return None
@@ -386,6 +387,15 @@ class LearnedGridTensorQuantizer:
             adjusted_min = scale * offset
             emax = emax - emin + adjusted_min
             emin = adjusted_min
+        return emin, emax, scale, offset
+
+    def _compute_updated_encoding(self):
+        """v1/tensor_quantizer.py:775-819: delta / offset from the parameters with the forward's
+        torch float32 arithmetic; asymmetric ranges are moved onto the grid (min = delta * offset)."""
+        tensors = self.encoding_tensors()
+        if tensors is None:
+            return None
+        emin, emax, scale, offset = tensors
         rows = torch.stack([emin, emax, scale, offset]).cpu().tolist()   # one device->host copy
         encodings = []
         for mn, mx, dl, off in zip(*rows):

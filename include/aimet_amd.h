@@ -889,6 +889,69 @@ int aimet_qa_sq_err(const void* ref, const void* x, int64_t n, int io_dtype, dou
 /* Kernel launches aimet_qa_sq_err has issued in this process; reset != 0 zeroes it. */
 int aimet_qa_launch_count(int64_t* count, int reset);
 
+/* ---- BatchNorm re-estimation and BN fold to scale (aimet_torch/bn_reestimation.py,
+ * batch_norm_fold.py fold_all_batch_norms_to_scale) ------------------------------------------------
+ * Device pointers throughout. No atomics: the order of every addition is fixed by the sizes and the
+ * base alignment, so equal inputs give equal bits. */
+
+/* One training-mode BatchNorm forward that also accumulates its batch statistics. x and y are
+ * contiguous [outer][C][inner] (NCHW / NCL / NCDHW: (N, C, spatial); (N, C) and channels-last: (rows,
+ * C, 1)); gamma / beta may be NULL (ones / zeros); y == x is allowed. Per channel, n = outer * inner
+ * and the shift K = x[0][c][0]: D1 = sum (x - K), D2 = sum (x - K)^2 (difference, square and sums in
+ * double), mean = K + D1 / n, M2 = D2 - D1 * (D1 / n), var_b = M2 / n, var_u = M2 / (n - 1);
+ *   sum_mean_dev[c] += mean, sum_var_dev[c] += var_u (double);
+ *   a = (float) (gamma / sqrt(var_b + eps)), b = (float) (beta - mean * gamma / sqrt(var_b + eps)),
+ *   both evaluated in double and rounded once; y = fmaf(x, a, b).
+ * Three launches (partials, their fold, the normalisation), or one where a channel fits LDS
+ * (aimet_bnre_forward_form). Fails, launching nothing, when n < 2,
+ * when a size is not positive and when a channel has more than 2^31 - 1 elements. */
+int aimet_bnre_forward(const float* x, int64_t outer, int64_t C, int64_t inner, const float* gamma, const float* beta,
+                       float eps, float* y, double* sum_mean_dev, double* sum_var_dev, void* stream);
+
+/* Which form aimet_bnre_forward takes. Resident: wherever a channel's n floats fit LDS (n <= 15872),
+ * one launch, one workgroup per channel that keeps the channel in LDS between the sums and the
+ * normalisation, so x is read once. Streaming: the three launches above, any size. 0: the default
+ * (resident where it fits, the faster one there); 1: streaming everywhere; 2: as 0. Both forms meet
+ * the same error bounds; their sums differ in order, so in the last bits. For the study in
+ * benchmarks/bn_reestimation_models.py and the tests. */
+int aimet_bnre_forward_form(int form, int* previous);
+
+/* running_mean[c] = (float) (sum_mean[c] / count), running_var[c] = (float) (sum_var[c] / count),
+ * c < C: the averages over `count` batches of what aimet_bnre_forward accumulated. */
+typedef struct aimet_bnre_finish_job
+{
+    const double* sum_mean;
+    const double* sum_var;
+    float* running_mean;
+    float* running_var;
+    int64_t C;
+    double count;
+} aimet_bnre_finish_job;
+
+/* `count` BatchNorms (host table) in one launch, grid (channel block, job). */
+int aimet_bnre_finish(const aimet_bnre_finish_job* jobs, int64_t count, void* stream);
+
+/* One fold of aimet_bnre_fold_scale: `fold` (forward == 0) exactly as aimet_dfq_bn_fold folds it, the
+ * same bits; and with c = gamma / sqrt(var + eps) of output channel o (fp32, as the fold's scale), the
+ * channel's learned quantization range follows the weight: c >= 0: (min, max) = (min * c, max * c),
+ * otherwise (max * c, min * c), each product one rounded fp32 multiply. enc_min / enc_max: cout floats,
+ * updated in place. A channel whose sqrt(var + eps) is zero keeps weight, bias and range, and the job's
+ * status word is set to 1. */
+typedef struct aimet_bnre_fold_scale_job
+{
+    aimet_dfq_bn_fold_job fold;
+    float* enc_min;
+    float* enc_max;
+} aimet_bnre_fold_scale_job;
+
+/* `count` folds (host table, no two on the same weight or range) in one launch, grid (job, output
+ * channel). status_dev: `count` int32 in device memory, zeroed by the caller. */
+int aimet_bnre_fold_scale(const aimet_bnre_fold_scale_job* jobs, int64_t count, int32_t* status_dev, void* stream);
+
+/* Kernel launches aimet_bnre_forward (three a call, or one in the resident form), aimet_bnre_finish
+ * and aimet_bnre_fold_scale have issued in this process; reset != 0 zeroes it. */
+int aimet_bnre_launch_count(int64_t* count, int reset);
+
 #ifdef __cplusplus
 }
 #endif
