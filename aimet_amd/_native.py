@@ -98,6 +98,16 @@ class BnreFinishJobC(ctypes.Structure):
                 ("running_var", ctypes.c_void_p), ("C", ctypes.c_int64), ("count", ctypes.c_double)]
 
 
+class RnnStepJobC(ctypes.Structure):
+    """aimet_rnn_step_job."""
+    _fields_ = [("ig", ctypes.c_void_p), ("hg", ctypes.c_void_p), ("b_ih", ctypes.c_void_p), ("b_hh", ctypes.c_void_p),
+                ("h_prev", ctypes.c_void_p), ("c_prev", ctypes.c_void_p), ("h_next", ctypes.c_void_p),
+                ("c_next", ctypes.c_void_p), ("out", ctypes.c_void_p), ("lens", ctypes.c_void_p),
+                ("ig_step_stride", ctypes.c_int64), ("ig_row_stride", ctypes.c_int64),
+                ("hg_row_stride", ctypes.c_int64), ("out_step_stride", ctypes.c_int64),
+                ("out_row_stride", ctypes.c_int64), ("reverse", ctypes.c_int32)]
+
+
 class BnreFoldScaleJobC(ctypes.Structure):
     """aimet_bnre_fold_scale_job."""
     _fields_ = [("fold", DfqBnFoldJobC), ("enc_min", ctypes.c_void_p), ("enc_max", ctypes.c_void_p)]
@@ -259,6 +269,9 @@ _PROTOTYPES = {
     "aimet_bnre_finish": [ctypes.POINTER(BnreFinishJobC), _i64, _vp],
     "aimet_bnre_fold_scale": [ctypes.POINTER(BnreFoldScaleJobC), _i64, _vp, _vp],
     "aimet_bnre_launch_count": [_i64p, _int],
+    "aimet_rnn_step": [_int, ctypes.POINTER(RnnStepJobC), _int, _i64, _i64, _i64, _i64, _i64, _enc_p, _int, _enc_p,
+                       _int, _int, _vp],
+    "aimet_rnn_launch_count": [_i64p, _int],
 }
 _RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p}
 

@@ -37,6 +37,8 @@ from aimet_amd.quantizers import QuantizationDataType, QuantScheme, compute_enco
 ENCODING_VERSION = "0.6.1"
 DEFAULT_QUANTIZABLE_TYPES = (nn.Conv1d, nn.Conv2d, nn.Conv3d, nn.ConvTranspose1d, nn.ConvTranspose2d,
                              nn.ConvTranspose3d, nn.Linear)
+# wrapped in QcQuantizeRecurrent (aimet_amd/qc_quantize_recurrent.py), whatever `quantizable_types` holds
+RECURRENT_TYPES = (nn.RNN, nn.LSTM, nn.GRU)
 
 _SCHEME_NAMES = {"tf": QuantScheme.post_training_tf, "tf_enhanced": QuantScheme.post_training_tf_enhanced,
                  "percentile": QuantScheme.post_training_percentile}
@@ -175,6 +177,22 @@ class QuantizationSimModel:
                         w.enable_input_quantizers(True)   # model_input: is_input_quantized
                         first = False
                     setattr(parent, child_name, w)
+                elif isinstance(child, RECURRENT_TYPES):
+                    # v1/quantsim.py:86-90: recurrent layers get the recurrent wrapper
+                    from aimet_amd.qc_quantize_recurrent import QcQuantizeRecurrent
+                    if self._cfg["per_channel_quantization"]:
+                        raise NotImplementedError("QcQuantizeRecurrent: per-channel quantizers are not supported; "
+                                                  "%s cannot be simulated with per_channel_quantization set"
+                                                  % (parent_name + "." + child_name).lstrip("."))
+                    r = QcQuantizeRecurrent(child, default_param_bw, default_output_bw, rounding_mode, quant_scheme,
+                                            is_symmetric=self._cfg["act_symmetric"], data_type=default_data_type)
+                    for pq in set(r.param_quantizers.values()):   # the config's parameter settings, as above
+                        pq.use_symmetric_encodings = self._cfg["param_symmetric"]
+                    for q in r._all_quantizers():
+                        q.use_strict_symmetric = self._cfg["strict_symmetric"]
+                        q.use_unsigned_symmetric = self._cfg["unsigned_symmetric"]
+                    setattr(parent, child_name, r)
+                    first = False   # its input_l0 quantizer is on by default
         if dummy_input is not None:
             self._run_passthrough(dummy_input)
 
@@ -188,9 +206,17 @@ class QuantizationSimModel:
             if isinstance(m, QcQuantizeWrapper):
                 yield name, m
 
+    def recurrent_wrappers(self):
+        """The QcQuantizeRecurrent modules of the model; not QcQuantizeWrappers, so quant_wrappers()
+        (and with it AdaRound, SeqMSE, bias correction and the analyzer) does not see them."""
+        from aimet_amd.qc_quantize_recurrent import QcQuantizeRecurrent
+        for name, m in self.model.named_modules():
+            if isinstance(m, QcQuantizeRecurrent):
+                yield name, m
+
     def _run_passthrough(self, dummy_input):
         """Checks the wrapped model runs on the dummy input (no statistics are collected)."""
-        for _, w in self.quant_wrappers():
+        for _, w in list(self.quant_wrappers()) + list(self.recurrent_wrappers()):
             w.set_mode(QcQuantizeOpMode.PASSTHROUGH)
         with _eval_mode(self.model), torch.no_grad():
             if isinstance(dummy_input, (list, tuple)):
@@ -239,7 +265,13 @@ class QuantizationSimModel:
         elif sharded and not (torch.distributed.is_available() and torch.distributed.is_initialized()):
             raise RuntimeError("sharded calibration needs an initialised torch.distributed process group")
         wrappers = [w for _, w in self.quant_wrappers()]
+        recurrent = [w for _, w in self.recurrent_wrappers()]
         _reset_many(wrappers)
+        for w in recurrent:
+            w.reset_encodings()
+            w.set_mode(QcQuantizeOpMode.ANALYSIS)
+            if self._quant_scheme == QuantScheme.post_training_percentile:
+                w.set_percentile_value(self._percentile_value)
         for w in wrappers:
             w.set_mode(QcQuantizeOpMode.ANALYSIS)
             if self._quant_scheme == QuantScheme.post_training_percentile:
@@ -252,6 +284,8 @@ class QuantizationSimModel:
             for w in static:
                 w.__dict__["_stats_batch"] = batch
                 w.__dict__["_param_qdq_cache"] = qdq_cache
+            for w in recurrent:
+                w.__dict__["_stats_batch"] = batch
             hook = self.model.register_forward_hook(lambda *_: batch.end_forward())
             try:
                 forward_pass_callback(self.model, forward_pass_callback_args)
@@ -261,6 +295,8 @@ class QuantizationSimModel:
                 for w in static:
                     w.__dict__.pop("_stats_batch", None)
                     w.__dict__.pop("_param_qdq_cache", None)
+                for w in recurrent:
+                    w.__dict__.pop("_stats_batch", None)
                 _forget_unused_param_encodings(pre)
                 # what the calibration copied / exchanged (reported by the tests and bench.py)
                 self._last_calibration = {"sharded": batch.sharded, "world": world, "copied_elements": batch.copied,
@@ -271,6 +307,9 @@ class QuantizationSimModel:
                       for q in self._quantizers_of(w)]
         compute_encodings_batched(quantizers)
         for _, w in self.quant_wrappers():
+            w.set_mode(QcQuantizeOpMode.ACTIVE)
+        for w in recurrent:
+            w.compute_encoding()
             w.set_mode(QcQuantizeOpMode.ACTIVE)
         self.replace_wrappers_for_quantize_dequantize()
 
@@ -303,6 +342,16 @@ class QuantizationSimModel:
             for pname, e in w.export_param_encodings().items():
                 if e is not None:
                     params["%s.%s" % (name, pname)] = e
+        for name, w in self.recurrent_wrappers():
+            # parameters under <module>.<param>, activations under <module>.<tensor name>
+            for kind, encs in ((QUANTIZER_TYPE_INPUT, w.export_input_encodings()),
+                               (QUANTIZER_TYPE_OUTPUT, w.export_output_encodings())):
+                for tensor, e in encs.items():
+                    if e is not None:
+                        activation.setdefault("%s.%s" % (name, tensor), {}).setdefault(kind, {})["0"] = e[0]
+            for pname, e in w.export_param_encodings().items():
+                if e is not None:
+                    params["%s.%s" % (name, pname)] = e
         return {"version": ENCODING_VERSION, "activation_encodings": activation, "param_encodings": params,
                 "excluded_layers": list(self._excluded_layer_names),
                 "quantizer_args": self.quant_args}
@@ -328,11 +377,12 @@ class QuantizationSimModel:
     def exclude_layers_from_quantization(self, layers_to_exclude: List[nn.Module]):
         """v1/quantsim.py:731-751: every quantization wrapper inside the given layers is replaced by
         its original module; the wrappers' names are recorded as the excluded layers."""
+        from aimet_amd.qc_quantize_recurrent import QcQuantizeRecurrent
         names = {m: n for n, m in self.model.named_modules()}
         wrappers = []
         for layer in layers_to_exclude:
             for m in layer.modules():
-                if isinstance(m, QcQuantizeWrapper):
+                if isinstance(m, (QcQuantizeWrapper, QcQuantizeRecurrent)):   # the latter after its update_params
                     wrappers.append(m)
                     self._excluded_layer_names.append(names.get(m))
 
@@ -356,7 +406,8 @@ class QuantizationSimModel:
 
     def _original_state_dict(self):
         sd = self.model.state_dict()
-        return {k.replace("._module_to_wrap", ""): v for k, v in sd.items()}
+        # a recurrent wrapper holds the parameters itself; the module it wraps repeats them
+        return {k.replace("._module_to_wrap", ""): v for k, v in sd.items() if ".module_to_quantize." not in k}
 
     def load_encodings(self, encodings: Union[Dict, str, os.PathLike], strict: bool = True, partial: bool = True,
                        requires_grad: Optional[bool] = None, allow_overwrite: bool = True):
@@ -374,7 +425,9 @@ class QuantizationSimModel:
         if strict:
             keys = set(param_encodings) | set(activation_encodings)
             model_keys = {n.replace("._module_to_wrap", "") for n, _ in self.model.named_modules()} | \
-                         {n.replace("._module_to_wrap", "") for n, _ in self.model.named_parameters()}
+                         {n.replace("._module_to_wrap", "") for n, _ in self.model.named_parameters()} | \
+                         {"%s.%s" % (n, t) for n, w in self.recurrent_wrappers()
+                          for t in list(w.input_quantizers) + list(w.output_quantizers)}
             missing = keys - model_keys
             if missing:
                 raise RuntimeError("Encoding dictionary contains modules/parameters that doesn't exist in the "
@@ -391,6 +444,13 @@ class QuantizationSimModel:
                                           allow_overwrite)
             except RuntimeError as e:
                 raise RuntimeError("Encoding import failed for module: %s.\n%s" % (name, e)) from e
+        for name, w in self.recurrent_wrappers():
+            w.import_encodings({p: param_encodings["%s.%s" % (name, p)] for p in w.param_quantizers
+                                if "%s.%s" % (name, p) in param_encodings},
+                               {t: next(iter(kinds.values()))["0"] for t in list(w.input_quantizers) +
+                                list(w.output_quantizers) for kinds in [activation_encodings.get("%s.%s" % (name, t))]
+                                if kinds}, strict, partial)
+            w.set_mode(QcQuantizeOpMode.ACTIVE)
         for _, w in self.quant_wrappers():
             w.set_mode(QcQuantizeOpMode.ACTIVE)
 
@@ -403,9 +463,11 @@ class QuantizationSimModel:
     def _remove_quantization_wrappers(cls, starting_module: nn.Module, list_of_modules_to_exclude):
         """v1/quantsim.py:1490-1517: every wrapper among `list_of_modules_to_exclude` below
         `starting_module` is replaced by the module it wraps."""
+        from aimet_amd.qc_quantize_recurrent import QcQuantizeRecurrent
         for name, child in list(starting_module.named_children()):
-            if any(child is m for m in list_of_modules_to_exclude) and isinstance(child, QcQuantizeWrapper):
-                child = child.get_original_module()
+            if any(child is m for m in list_of_modules_to_exclude) and \
+                    isinstance(child, (QcQuantizeWrapper, QcQuantizeRecurrent)):
+                child = child.get_original_module()   # a recurrent wrapper's, after its update_params
                 setattr(starting_module, name, child)
             cls._remove_quantization_wrappers(child, list_of_modules_to_exclude)
 

@@ -952,6 +952,59 @@ int aimet_bnre_fold_scale(const aimet_bnre_fold_scale_job* jobs, int64_t count, 
  * and aimet_bnre_fold_scale have issued in this process; reset != 0 zeroes it. */
 int aimet_bnre_launch_count(int64_t* count, int reset);
 
+/* ---- quantized recurrent layers (aimet_torch/v1/qc_quantize_recurrent.py) -------------------------
+ * One fused time step of an RNN / LSTM / GRU layer for up to AIMET_RNN_MAX_JOBS independent jobs
+ * (the directions of a bidirectional layer) in one launch. Gate order as torch: LSTM i, f, g, o;
+ * GRU r, z, n. Per job and row b < B, with t = step (forward) or len(b) - 1 - step (reverse;
+ * len(b) = lens[b], or T when lens is null), ig = the row's G H floats at
+ * ig[t * ig_step_stride + b * ig_row_stride], hg those at hg[b * hg_row_stride]:
+ *   LSTM      g = (ig + b_ih) + (hg + b_hh); c' = sigmoid(g_f) * c + sigmoid(g_i) * tanh(g_g);
+ *             h' = sigmoid(g_o) * tanh(c')
+ *   GRU       r = sigmoid((hg_r + b_hh_r) + (ig_r + b_ih_r)), z likewise;
+ *             n = tanh((ig_n + b_ih_n) + (hg_n + b_hh_n) * r); h' = (h - n) * z + n
+ *   RNN_TANH  h' = tanh((hg + b_hh) + (ig + b_ih));  RNN_RELU  h' = max(that sum, 0)
+ * in float32, every operation rounded once in the order written; sigmoid and tanh are the
+ * written-out functions of csrc/rnn_math.hpp (no math library). A null bias is not added. Rows at
+ * or beyond valid_rows keep h and c (the sequences that have ended, rows sorted by descending
+ * length). Then, when op_mode is ACTIVE and the quantizer is enabled, h (and c) of every row go
+ * through the per-tensor QDQ of aimet_qdq_per_tensor (nearest) with h_enc (c_enc). h' and c' are
+ * written to h_next and c_next ([B, H] contiguous; may be h_prev and c_prev), and h' of the rows
+ * below valid_rows to out[t * out_step_stride + b * out_row_stride] (the job's column offset in
+ * the [T, B, D H] slab is part of `out`); nothing else is written. Pointers need 4-byte alignment
+ * only. c_prev / c_next / c_enc are read for LSTM alone. */
+enum aimet_rnn_mode { AIMET_RNN_LSTM = 0, AIMET_RNN_GRU = 1, AIMET_RNN_TANH = 2, AIMET_RNN_RELU = 3 };
+enum aimet_rnn_op_mode { AIMET_RNN_OP_PASSTHROUGH = 1, AIMET_RNN_OP_ANALYSIS = 2, AIMET_RNN_OP_ACTIVE = 3 };
+#define AIMET_RNN_MAX_JOBS 2
+
+typedef struct aimet_rnn_step_job
+{
+    const float* ig;     /* x W_ih^T of every step, no bias */
+    const float* hg;     /* h_prev W_hh^T of this step, no bias */
+    const float* b_ih;   /* G H floats, or null */
+    const float* b_hh;
+    const float* h_prev;
+    const float* c_prev;
+    float* h_next;
+    float* c_next;
+    float* out;
+    const int32_t* lens; /* B sequence lengths in device memory (descending), or null: all T */
+    int64_t ig_step_stride;
+    int64_t ig_row_stride;
+    int64_t hg_row_stride;
+    int64_t out_step_stride;
+    int64_t out_row_stride;
+    int32_t reverse;
+} aimet_rnn_step_job;
+
+/* jobs: host table of `count` (1 or 2) jobs; it travels in the kernel arguments (no copy, no
+ * allocation: a captured step loop is a linear chain of kernel nodes). */
+int aimet_rnn_step(int mode, const aimet_rnn_step_job* jobs, int count, int64_t B, int64_t H, int64_t T, int64_t step,
+                   int64_t valid_rows, const aimet_tf_encoding* h_enc, int h_enabled, const aimet_tf_encoding* c_enc,
+                   int c_enabled, int op_mode, void* stream);
+
+/* Kernel launches aimet_rnn_step has issued in this process; reset != 0 zeroes it. */
+int aimet_rnn_launch_count(int64_t* count, int reset);
+
 #ifdef __cplusplus
 }
 #endif
