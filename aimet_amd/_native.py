@@ -272,8 +272,12 @@ _PROTOTYPES = {
     "aimet_rnn_step": [_int, ctypes.POINTER(RnnStepJobC), _int, _i64, _i64, _i64, _i64, _i64, _enc_p, _int, _enc_p,
                        _int, _int, _vp],
     "aimet_rnn_launch_count": [_i64p, _int],
+    "aimet_attn_softmax": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _vp, _enc_p, _enc_p, _vp],
+    "aimet_attn_softmax_max_s": [],
+    "aimet_attn_launch_count": [_i64p, _int],
 }
-_RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p}
+_RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p,
+             "aimet_attn_softmax_max_s": ctypes.c_int64}
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
 

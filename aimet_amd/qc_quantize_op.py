@@ -650,6 +650,51 @@ class StaticGridQuantWrapper(QcQuantizeWrapper):
             outputs.append(inner(t, index))
         return outputs
 
+    # -- a caller that computes the wrapped module's output itself (aimet_amd.transformers) ----------
+    def output_fusable(self) -> bool:
+        """True when a caller may replace this wrapper's forward by a kernel of its own that applies
+        the output quantizer: nothing but output quantizer 0 would act in the forward (no enabled
+        input or parameter quantizer), and that one is disabled or a per-tensor integer static-grid
+        quantizer rounding to nearest."""
+        if len(self.output_quantizers) != 1 or any(q.enabled for q in self.input_quantizers) or \
+                any(q.enabled for q in self.param_quantizers.values()):
+            return False
+        q = self.output_quantizers[0]
+        if not q.enabled:
+            return True
+        stochastic = self.training and q.round_mode != RoundingMode.ROUND_NEAREST
+        return type(q) is StaticGridPerTensorQuantizer and q.data_type == QuantizationDataType.int and \
+            q.bitwidth != 32 and not stochastic
+
+    def fused_output_encoding(self):
+        """One forward whose arithmetic the caller fuses (output_fusable() holds): it counts as a
+        forward for compute_encodings, and the result is the encoding the caller's kernel must apply
+        to the output, or None where forward() would return it unquantized (PASSTHROUGH, a disabled
+        quantizer, ANALYSIS without a frozen encoding; the caller then hands the unquantized output
+        to observe_output)."""
+        ran = self.__dict__.get("_analysis_ran")
+        if ran is not None:
+            ran[0] = True
+        q = self.output_quantizers[0]
+        if not q.enabled or self._mode is QcQuantizeOpMode.PASSTHROUGH or \
+                (self._mode is QcQuantizeOpMode.ANALYSIS and not q.is_encoding_frozen):
+            return None
+        if q.encoding is None:
+            raise RuntimeError("the output quantizer of %s has no encoding; run compute_encodings first"
+                               % type(self._module_to_wrap).__name__)
+        return q.encoding
+
+    def observe_output(self, output):
+        """The unquantized output of a fused forward to the output quantizer's statistics, the way
+        forward() sends it in ANALYSIS mode (StatsBatch, sharded calibration); nothing in the other
+        modes. True when the statistics took the tensor: they may read it after this call returns,
+        so the caller must not write to it."""
+        q = self.output_quantizers[0]
+        if self._mode is QcQuantizeOpMode.ANALYSIS and q.enabled and not q.is_encoding_frozen:
+            self._quantize_activation(self.output_quantizers, [output])
+            return True
+        return False
+
     def enable_per_channel_quantization(self):
         """v1/qc_quantize_op.py:899-923."""
         new = {}

@@ -1005,6 +1005,35 @@ int aimet_rnn_step(int mode, const aimet_rnn_step_job* jobs, int count, int64_t 
 /* Kernel launches aimet_rnn_step has issued in this process; reset != 0 zeroes it. */
 int aimet_rnn_launch_count(int64_t* count, int reset);
 
+/* ---- quantizable multi-head attention (aimet_torch/transformers/activation.py) ------------------
+ * The score quantizer, both masks, the softmax and the probability quantizer of one attention block
+ * in one launch over scores [B H, L, S] (float32, contiguous). Per row r = bh L + l, b = bh / H:
+ *   x_j = QDQ(scores_j; score_enc)       the arithmetic of aimet_qdq_per_tensor, nearest
+ *   x_j = -inf where attn_mask[((attn_mask_per_bh ? bh : 0) L + l) S + j] or key_padding_mask[b S + j]
+ *         is non-zero (one byte an element; either table may be null)
+ *   m = max_j x_j;  e_j = exp_r(x_j - m) of csrc/rnn_math.hpp, and exactly 0 where x_j is -inf
+ *   s = sum_j e_j in a fixed order that depends on S alone:
+ *       S <= 1024: lane t of 64 adds the elements t, t + 64, t + 128, ... in increasing index (a lane
+ *       without elements holds +0); then v_t = v_t + v_(t xor d) for d = 32, 16, 8, 4, 2, 1.
+ *       S > 1024: thread t of 256 adds t, t + 256, ... in increasing index; each group of 64
+ *       consecutive threads runs the six steps above, giving w0..w3; s = (w0 + w1) + (w2 + w3).
+ *   probs_j = QDQ(e_j / s; prob_enc)     IEEE divide; a row with every position masked is 0 / 0 = NaN
+ *                                        before the QDQ
+ * A null encoding skips its QDQ. probs may be scores. Pointers need 4-byte alignment only. Each row
+ * is read once and written once and stays on chip in between; S above AIMET_ATTN_SOFTMAX_MAX_S is
+ * AIMET_ERR_INVALID_ARGUMENT and nothing is written. */
+#define AIMET_ATTN_SOFTMAX_MAX_S 16320
+
+int aimet_attn_softmax(const float* scores, float* probs, int64_t B, int64_t H, int64_t L, int64_t S,
+                       const uint8_t* attn_mask, int attn_mask_per_bh, const uint8_t* key_padding_mask,
+                       const aimet_tf_encoding* score_enc, const aimet_tf_encoding* prob_enc, void* stream);
+
+/* AIMET_ATTN_SOFTMAX_MAX_S of the loaded library. */
+int64_t aimet_attn_softmax_max_s(void);
+
+/* Kernel launches aimet_attn_softmax has issued in this process; reset != 0 zeroes it. */
+int aimet_attn_launch_count(int64_t* count, int reset);
+
 #ifdef __cplusplus
 }
 #endif
