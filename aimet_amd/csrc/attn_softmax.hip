@@ -35,7 +35,6 @@
 // often odd, so consecutive rows have different alignments); the fixed-order sum then reads LDS by
 // element index. 64-bit offsets throughout; rows are taken in a grid-stride loop. In place
 // (probs == scores) is safe on both paths: a row is read completely before any of it is written.
-#include <atomic>
 
 #include "common.hpp"
 #include "rnn_math.hpp"
@@ -56,7 +55,7 @@ constexpr unsigned kMaxGrid = 1u << 16;
 
 static_assert((kMaxS % 4) == 0 && kMaxS * 4 + 16 <= 65536, "a row and the partial sums must fit 64 KiB of LDS");
 
-std::atomic<int64_t> g_launches {0};
+LaunchCounter g_launches;
 
 struct Args
 {
@@ -338,7 +337,7 @@ int aimet_attn_softmax(const float* scores, float* probs, int64_t B, int64_t H, 
             attn_softmax_lds<<<grid, kBlk, lds, s>>>(a);
         }
         AIMET_LAUNCH_CHECK();
-        g_launches.fetch_add(1, std::memory_order_relaxed);
+        g_launches.add(1);
     });
 }
 
@@ -349,12 +348,7 @@ int64_t aimet_attn_softmax_max_s(void)
 
 int aimet_attn_launch_count(int64_t* count, int reset)
 {
-    return guarded([&] {
-        const int64_t n = reset ? g_launches.exchange(0, std::memory_order_relaxed)
-                                : g_launches.load(std::memory_order_relaxed);
-        if (count)
-            *count = n;
-    });
+    return guarded([&] { g_launches.read(count, reset); });
 }
 
 }   // extern "C"

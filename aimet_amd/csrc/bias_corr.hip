@@ -3,183 +3,27 @@
 // the host and takes float32 numpy means there).
 //
 //  * aimet_bc_channel_sums: acc[c] += sum over a layer output of channel c, in double. One HBM read of
-//    the tensor, nothing else. Two layouts, two kernels: planar ([outer][C][inner], NCHW) gives a
-//    workgroup one (channel, split) and reads the channel's segments in 16-byte loads between a scalar
-//    head and tail; interleaved ([rows][C], Linear and channels-last) gives a lane its columns and a
-//    workgroup a range of rows. Both leave one double per (split, channel); a second, tiny launch
-//    folds the splits in order into acc. No atomics: the order of every addition is fixed by the
-//    sizes (and, for the choice between 16-byte and 4-byte loads, the base alignment) alone.
+//    the tensor, nothing else: the ChannelSum accumulator on the traversals of channel_reduce.hpp
+//    (planar long / planar short / interleaved), which leave one double per (split, channel); a
+//    second, tiny launch folds the splits in order into acc. No atomics: the order of every addition
+//    is fixed by the sizes (and, for the choice between 16-byte and 4-byte loads, the base alignment)
+//    alone.
 //  * aimet_bc_apply_empirical: bias[c] -= (q_sum[c] - ref_sum[c]) / count, rounded to fp32 once.
 //  * aimet_bc_analytical: the BN-based correction of `count` layers in one launch, grid (job, output
 //    channel): fp32 differences of the two weights, everything after in double.
-#include <atomic>
 #include <cmath>
 #include <vector>
 
-#include "common.hpp"
+#include "channel_reduce.hpp"
 
 namespace aimet_amd
 {
 namespace
 {
 
-constexpr int kBcBlock         = 256;
-constexpr int64_t kPieceFloats = 4096;   // planar: floats of one segment a workgroup takes at a time
-constexpr int64_t kMinPerGroup = 8192;   // elements below which a further split is not worth a workgroup
-constexpr int64_t kVecInner    = 128;    // planar segments shorter than this are read flat, 4 bytes a lane
+constexpr int kBcBlock = kReduceBlock;
 
-std::atomic<int64_t> g_launches {0};
-
-// Fixed-shape tree over the workgroup's 256 partials; lane 0's return value is the sum.
-__device__ __forceinline__ double block_sum(double v, double* lds)
-{
-    const int t = threadIdx.x;
-    lds[t]      = v;
-    __syncthreads();
-    for (int s = kBcBlock / 2; s > 0; s >>= 1)
-    {
-        if (t < s)
-            lds[t] = lds[t] + lds[t + s];
-        __syncthreads();
-    }
-    const double r = lds[0];
-    __syncthreads();
-    return r;
-}
-
-// ---- planar, long segments: workgroup (c, split) takes pieces split, split + nsplit, ... of the
-// channel's outer * pieces_per_seg pieces; a piece is piece_len floats of one segment (the last
-// piece of a segment shorter).
-__global__ __launch_bounds__(kBcBlock) void bc_planar_vec_kernel(const float* __restrict__ x, int64_t outer, int64_t C,
-                                                                 int64_t inner, int64_t pieces_per_seg,
-                                                                 int64_t piece_len, double* __restrict__ part)
-{
-    __shared__ double lds[kBcBlock];
-    const int t          = threadIdx.x;
-    const int64_t c      = blockIdx.x;
-    const int64_t npiece = outer * pieces_per_seg;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    for (int64_t q = blockIdx.y; q < npiece; q += gridDim.y)
-    {
-        const int64_t o     = q / pieces_per_seg;
-        const int64_t start = (q - o * pieces_per_seg) * piece_len;
-        const int64_t n     = (inner - start) < piece_len ? (inner - start) : piece_len;
-        const float* p      = x + (o * C + c) * inner + start;
-        int64_t head        = (int64_t) (((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2);
-        if (head > n)
-            head = n;
-        if (t < head)
-            a0 = a0 + (double) p[t];
-        const float4* v  = reinterpret_cast<const float4*>(p + head);
-        const int64_t nv = (n - head) >> 2;
-#pragma unroll 4
-        for (int64_t i = t; i < nv; i += kBcBlock)
-        {
-            const float4 f = v[i];
-            a0             = a0 + (double) f.x;
-            a1             = a1 + (double) f.y;
-            a2             = a2 + (double) f.z;
-            a3             = a3 + (double) f.w;
-        }
-        const int64_t rest = head + nv * 4 + t;   // at most three floats
-        if (rest < n)
-            a1 = a1 + (double) p[rest];
-    }
-    const double s = block_sum((a0 + a1) + (a2 + a3), lds);
-    if (t == 0)
-        part[(int64_t) blockIdx.y * C + c] = s;
-}
-
-// ---- planar, short segments: the channel's outer * inner elements as one flat range, workgroup
-// (c, split) takes `chunk` of them; consecutive lanes read consecutive floats of a segment.
-__global__ __launch_bounds__(kBcBlock) void bc_planar_flat_kernel(const float* __restrict__ x, int64_t C, int64_t inner,
-                                                                  FastDiv by_inner, int64_t n, int64_t chunk,
-                                                                  double* __restrict__ part)
-{
-    __shared__ double lds[kBcBlock];
-    const int64_t c      = blockIdx.x;
-    const int64_t lo     = (int64_t) blockIdx.y * chunk;
-    const int64_t hi     = lo + chunk < n ? lo + chunk : n;
-    const int64_t stride = C * inner;
-    const float* base    = x + c * inner;
-    double a0 = 0.0, a1 = 0.0;
-    int64_t e = lo + threadIdx.x;
-    for (; e + kBcBlock < hi; e += 2 * kBcBlock)
-    {
-        const uint32_t o0 = by_inner.div((uint32_t) e), o1 = by_inner.div((uint32_t) (e + kBcBlock));
-        const float f0 = base[(int64_t) o0 * stride + (e - (int64_t) o0 * inner)];
-        const float f1 = base[(int64_t) o1 * stride + (e + kBcBlock - (int64_t) o1 * inner)];
-        a0             = a0 + (double) f0;
-        a1             = a1 + (double) f1;
-    }
-    if (e < hi)
-    {
-        const uint32_t o0 = by_inner.div((uint32_t) e);
-        a0                = a0 + (double) base[(int64_t) o0 * stride + (e - (int64_t) o0 * inner)];
-    }
-    const double s = block_sum(a0 + a1, lds);
-    if (threadIdx.x == 0)
-        part[(int64_t) blockIdx.y * C + c] = s;
-}
-
-// ---- interleaved: [rows][C]. The 256 lanes are LY rows x LX column units (a unit is VEC columns);
-// workgroup (bx, split) owns column units bx * LX .. and the rows split * rows_per .. ; lane (ty, tx)
-// adds the rows ty, ty + LY, ... of its range, then a fixed tree over ty.
-template <int VEC>
-__global__ __launch_bounds__(kBcBlock) void bc_interleaved_kernel(const float* __restrict__ x, int64_t rows, int64_t C,
-                                                                  int lx_log2, int64_t rows_per,
-                                                                  double* __restrict__ part)
-{
-    __shared__ double lds[kBcBlock * VEC];
-    const int t = threadIdx.x, LX = 1 << lx_log2, LY = kBcBlock >> lx_log2;
-    const int tx = t & (LX - 1), ty = t >> lx_log2;
-    const int64_t unit  = (int64_t) blockIdx.x * LX + tx;
-    const int64_t col   = unit * VEC;
-    const int64_t r0    = (int64_t) blockIdx.y * rows_per;
-    const int64_t r1    = r0 + rows_per < rows ? r0 + rows_per : rows;
-    double a[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k)
-        a[k] = 0.0;
-    if (col < C)
-    {
-#pragma unroll 4
-        for (int64_t r = r0 + ty; r < r1; r += LY)
-        {
-            const float* p = x + r * C + col;
-            if (VEC == 4)
-            {
-                const float4 f = *reinterpret_cast<const float4*>(p);
-                a[0]           = a[0] + (double) f.x;
-                a[1 % VEC]     = a[1 % VEC] + (double) f.y;
-                a[2 % VEC]     = a[2 % VEC] + (double) f.z;
-                a[3 % VEC]     = a[3 % VEC] + (double) f.w;
-            }
-            else
-                a[0] = a[0] + (double) *p;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < VEC; ++k)
-        lds[k * kBcBlock + t] = a[k];
-    __syncthreads();
-    for (int s = LY >> 1; s > 0; s >>= 1)
-    {
-        if (ty < s)
-        {
-#pragma unroll
-            for (int k = 0; k < VEC; ++k)
-                lds[k * kBcBlock + t] = lds[k * kBcBlock + t] + lds[k * kBcBlock + t + s * LX];
-        }
-        __syncthreads();
-    }
-    if (ty == 0 && col < C)
-    {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k)
-            part[(int64_t) blockIdx.y * C + col + k] = lds[k * kBcBlock + t];
-    }
-}
+LaunchCounter g_launches;
 
 // acc[c] += part[0][c] + part[1][c] + ... , in that order
 __global__ __launch_bounds__(kBcBlock) void bc_fold_kernel(const double* __restrict__ part, int64_t nsplit, int64_t C,
@@ -265,19 +109,6 @@ __global__ __launch_bounds__(kBcBlock) void bc_analytical_kernel(const AnaJob* j
         j.bias[o] = (float) ((double) j.bias[o] - err);
 }
 
-// ---- host side ---------------------------------------------------------------------------------------
-int64_t clamp64(int64_t v, int64_t lo, int64_t hi)
-{
-    return v < lo ? lo : (v > hi ? hi : v);
-}
-
-// splits of a channel of n elements when `groups` workgroups exist per split: fill the chip, but
-// leave every workgroup kMinPerGroup elements
-int64_t split_count(int64_t groups, int64_t n, int64_t most)
-{
-    return clamp64(std::min(ceil_div(kMaxStreamBlocks, groups), ceil_div(n, kMinPerGroup)), 1, std::min<int64_t>(most, 65535));
-}
-
 void fold(const double* part, int64_t nsplit, int64_t C, double* acc, hipStream_t s)
 {
     bc_fold_kernel<<<(unsigned) ceil_div(C, kBcBlock), kBcBlock, 0, s>>>(part, nsplit, C, acc);
@@ -293,58 +124,12 @@ extern "C" {
 int aimet_bc_channel_sums(const float* x, int64_t outer, int64_t C, int64_t inner, double* acc_dev, void* stream)
 {
     return guarded([&] {
-        AIMET_REQUIRE(outer > 0 && C > 0 && inner > 0, "channel sums: outer, C and inner must be positive");
-        AIMET_REQUIRE(C < (int64_t(1) << 31) && outer < (int64_t(1) << 31) && inner < (int64_t(1) << 31) &&
-                          outer * inner < (int64_t(1) << 31) && outer * inner < (int64_t(1) << 46) / C,
-                      "channel sums: too large (2^31 elements per channel, 2^46 in all)");
+        require_channel_sizes("channel sums", outer, C, inner);
         require_device_ptr(x, "channel sums input");
         require_device_ptr(acc_dev, "channel sums accumulator");
-        AIMET_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(acc_dev) & 7) == 0,
-                      "channel sums: misaligned pointer");
-        hipStream_t s = as_stream(stream);
-        int64_t nsplit;
-        double* part;
-        if (inner == 1)
-        {
-            const int64_t rows = outer;
-            const bool vec     = (C & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-            const int64_t units = vec ? C / 4 : C;
-            int lx_log2         = 0;
-            while (lx_log2 < 8 && (int64_t(1) << lx_log2) < units)
-                ++lx_log2;
-            const int64_t LX = int64_t(1) << lx_log2, LY = kBcBlock / LX;
-            const int64_t gx = ceil_div(units, LX);
-            AIMET_REQUIRE(gx < (int64_t(1) << 31), "channel sums: too many channels");
-            nsplit                 = split_count(gx, rows * LX * (vec ? 4 : 1), ceil_div(rows, LY));
-            const int64_t rows_per = ceil_div(rows, nsplit);
-            nsplit                 = ceil_div(rows, rows_per);
-            part                   = static_cast<double*>(scratch_alloc((size_t) (nsplit * C) * sizeof(double), s));
-            const dim3 grid((unsigned) gx, (unsigned) nsplit);
-            if (vec)
-                bc_interleaved_kernel<4><<<grid, kBcBlock, 0, s>>>(x, rows, C, lx_log2, rows_per, part);
-            else
-                bc_interleaved_kernel<1><<<grid, kBcBlock, 0, s>>>(x, rows, C, lx_log2, rows_per, part);
-        }
-        else if (inner >= kVecInner)
-        {
-            const int64_t pieces_per_seg = ceil_div(inner, kPieceFloats);
-            const int64_t piece_len      = ceil_div(ceil_div(inner, pieces_per_seg), 4) * 4;
-            const int64_t pps            = ceil_div(inner, piece_len);
-            nsplit                       = split_count(C, outer * inner, outer * pps);
-            part = static_cast<double*>(scratch_alloc((size_t) (nsplit * C) * sizeof(double), s));
-            bc_planar_vec_kernel<<<dim3((unsigned) C, (unsigned) nsplit), kBcBlock, 0, s>>>(x, outer, C, inner, pps,
-                                                                                           piece_len, part);
-        }
-        else
-        {
-            const int64_t n     = outer * inner;
-            nsplit              = split_count(C, n, ceil_div(n, kBcBlock));
-            const int64_t chunk = ceil_div(ceil_div(n, nsplit), kBcBlock) * kBcBlock;
-            nsplit              = ceil_div(n, chunk);
-            part = static_cast<double*>(scratch_alloc((size_t) (nsplit * C) * sizeof(double), s));
-            bc_planar_flat_kernel<<<dim3((unsigned) C, (unsigned) nsplit), kBcBlock, 0, s>>>(
-                x, C, inner, FastDiv((uint32_t) inner), n, chunk, part);
-        }
+        require_channel_alignment("channel sums", {x}, {acc_dev});
+        hipStream_t s             = as_stream(stream);
+        const auto [part, nsplit] = launch_channel_reduce<ChannelSum>(x, outer, C, inner, s);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess)
         {
@@ -353,7 +138,7 @@ int aimet_bc_channel_sums(const float* x, int64_t outer, int64_t C, int64_t inne
         }
         scratch_free(part, s);
         AIMET_HIP_CHECK(e);
-        g_launches.fetch_add(2, std::memory_order_relaxed);
+        g_launches.add(2);
     });
 }
 
@@ -369,7 +154,7 @@ int aimet_bc_apply_empirical(float* bias, const double* ref_sum, const double* q
         bc_apply_empirical_kernel<<<(unsigned) ceil_div(C, kBcBlock), kBcBlock, 0, as_stream(stream)>>>(
             bias, ref_sum, q_sum, C, count);
         AIMET_LAUNCH_CHECK();
-        g_launches.fetch_add(1, std::memory_order_relaxed);
+        g_launches.add(1);
     });
 }
 
@@ -417,18 +202,13 @@ int aimet_bc_analytical(const aimet_bc_analytical_job* jobs, int64_t count, void
         hipError_t e = hipGetLastError();
         scratch_free(dev, s);
         AIMET_HIP_CHECK(e);
-        g_launches.fetch_add(1, std::memory_order_relaxed);
+        g_launches.add(1);
     });
 }
 
 int aimet_bc_launch_count(int64_t* count, int reset)
 {
-    return guarded([&] {
-        const int64_t n = reset ? g_launches.exchange(0, std::memory_order_relaxed)
-                                : g_launches.load(std::memory_order_relaxed);
-        if (count)
-            *count = n;
-    });
+    return guarded([&] { g_launches.read(count, reset); });
 }
 
 }   // extern "C"

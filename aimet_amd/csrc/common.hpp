@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
@@ -263,6 +264,25 @@ void fold_buffers_release(const FoldBuffers& f, hipStream_t s);
 // aimet_capture_pool_limit: the capture arena's cap on the current device (returns the previous one)
 size_t capture_pool_limit(size_t arena_floats);
 void scratch_free(void* p, hipStream_t s);
+
+// Kernel launches of one family of entry points, as its aimet_*_launch_count reports them.
+class LaunchCounter
+{
+    std::atomic<int64_t> n_ {0};
+
+public:
+    void add(int64_t n)
+    {
+        n_.fetch_add(n, std::memory_order_relaxed);
+    }
+    // the count into *count (where given), zeroed behind it on `reset`
+    void read(int64_t* count, int reset)
+    {
+        const int64_t n = reset ? n_.exchange(0, std::memory_order_relaxed) : n_.load(std::memory_order_relaxed);
+        if (count)
+            *count = n;
+    }
+};
 
 // bn_reest.hip: adds to the count aimet_bnre_launch_count reports (the fold to scale lives in dfq.hip)
 void bnre_count_launches(int64_t n);

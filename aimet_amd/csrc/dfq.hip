@@ -9,7 +9,6 @@
 // read served by the cache. The reductions are LDS trees of a fixed shape: no atomics, equal inputs
 // give equal bits. Arithmetic: each product, quotient and root rounded on its own in fp32
 // (-ffp-contract=off, correctly rounded divide and sqrt), denormals kept, as numpy on the host.
-#include <atomic>
 #include <cmath>
 #include <vector>
 
@@ -22,7 +21,7 @@ namespace
 
 constexpr int kDfqBlock = 256;
 
-std::atomic<int64_t> g_launches {0};
+LaunchCounter g_launches;
 
 // One channel's elements: nseg segments of len floats, segment j at base + j * stride.
 struct Span
@@ -413,7 +412,7 @@ int aimet_dfq_bn_fold(const aimet_dfq_bn_fold_job* jobs, int64_t count, int32_t*
         hipError_t e = hipGetLastError();
         scratch_free(dev, s);
         AIMET_HIP_CHECK(e);
-        g_launches.fetch_add(1, std::memory_order_relaxed);
+        g_launches.add(1);
     });
 }
 
@@ -465,7 +464,7 @@ int aimet_dfq_cls_pair(const aimet_dfq_weight* w0, float* bias0, const aimet_dfq
         dfq_cls_pair_kernel<<<(unsigned) w0->cout, kDfqBlock, 0, as_stream(stream)>>>(out_side(*w0), bias0,
                                                                                      in_side(*w1), scale_dev);
         AIMET_LAUNCH_CHECK();
-        g_launches.fetch_add(1, std::memory_order_relaxed);
+        g_launches.add(1);
     });
 }
 
@@ -489,7 +488,7 @@ int aimet_dfq_cls_triple(const aimet_dfq_weight* w0, float* bias0, const aimet_d
         dfq_cls_triple_kernel<<<(unsigned) w0->cout, kDfqBlock, 0, as_stream(stream)>>>(
             out_side(*w0), bias0, out_side(*w1), bias1, in_side(*w2), s12_dev, s23_dev);
         AIMET_LAUNCH_CHECK();
-        g_launches.fetch_add(1, std::memory_order_relaxed);
+        g_launches.add(1);
     });
 }
 
@@ -510,18 +509,13 @@ int aimet_dfq_bias_fold(const float* gamma, const float* beta, const float* scal
             gamma, beta, scale, C, relu_between ? 1 : 0, bias1, w2->data, w2->cin, w2->k, w2->out_stride,
             w2->in_stride, bias2);
         AIMET_LAUNCH_CHECK();
-        g_launches.fetch_add(1, std::memory_order_relaxed);
+        g_launches.add(1);
     });
 }
 
 int aimet_dfq_launch_count(int64_t* count, int reset)
 {
-    return guarded([&] {
-        const int64_t n = reset ? g_launches.exchange(0, std::memory_order_relaxed)
-                                : g_launches.load(std::memory_order_relaxed);
-        if (count)
-            *count = n;
-    });
+    return guarded([&] { g_launches.read(count, reset); });
 }
 
 }   // extern "C"

@@ -12,7 +12,6 @@
 //    consecutive partials in index order, then a fixed tree), multiplies by scale once and adds into
 //    acc. No atomics: the order of every addition is fixed by n, the dtype and the two base
 //    alignments, so two runs on the same pointers give the same bits.
-#include <atomic>
 
 #include "common.hpp"
 #include "io16.hpp"
@@ -26,7 +25,7 @@ constexpr int kQaBlock          = 256;
 constexpr int64_t kQaVecPerLane = 2;   // 16-byte loads per input a lane has before the grid grows no further
 constexpr int64_t kQaMaxElems   = int64_t(1) << 40;
 
-std::atomic<int64_t> g_launches {0};
+LaunchCounter g_launches;
 
 // Fixed-shape tree over the workgroup's 256 pairs; every lane returns with lds[0], lds[kQaBlock] the sums.
 __device__ __forceinline__ void block_sum2(double a, double b, double* lds)
@@ -206,7 +205,7 @@ void launch_sq_err(const void* ref_v, const void* x_v, int64_t n, double scale, 
     }
     scratch_free(part, s);
     AIMET_HIP_CHECK(e);
-    g_launches.fetch_add(2, std::memory_order_relaxed);
+    g_launches.add(2);
 }
 
 }   // namespace
@@ -242,12 +241,7 @@ int aimet_qa_sq_err(const void* ref, const void* x, int64_t n, int io_dtype, dou
 
 int aimet_qa_launch_count(int64_t* count, int reset)
 {
-    return guarded([&] {
-        const int64_t n = reset ? g_launches.exchange(0, std::memory_order_relaxed)
-                                : g_launches.load(std::memory_order_relaxed);
-        if (count)
-            *count = n;
-    });
+    return guarded([&] { g_launches.read(count, reset); });
 }
 
 }   // extern "C"

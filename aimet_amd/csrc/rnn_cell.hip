@@ -17,7 +17,6 @@
 //    need only 4-byte alignment, so any H and any base work), the last lane of a row the H mod 4
 //    columns left, one at a time. No LDS, no atomics, no grid-wide synchronisation; the job table
 //    travels in the kernel arguments, so a captured step loop is a chain of plain kernel nodes.
-#include <atomic>
 
 #include "common.hpp"
 #include "rnn_math.hpp"
@@ -32,7 +31,7 @@ namespace
 
 constexpr int kBlk = 256;
 
-std::atomic<int64_t> g_launches {0};
+LaunchCounter g_launches;
 
 // four floats that need the alignment of one
 struct F4
@@ -295,18 +294,13 @@ int aimet_rnn_step(int mode, const aimet_rnn_step_job* jobs, int count, int64_t 
         default: rnn_step_kernel<AIMET_RNN_RELU><<<grid, kBlk, 0, s>>>(a); break;
         }
         AIMET_LAUNCH_CHECK();
-        g_launches.fetch_add(1, std::memory_order_relaxed);
+        g_launches.add(1);
     });
 }
 
 int aimet_rnn_launch_count(int64_t* count, int reset)
 {
-    return guarded([&] {
-        const int64_t n = reset ? g_launches.exchange(0, std::memory_order_relaxed)
-                                : g_launches.load(std::memory_order_relaxed);
-        if (count)
-            *count = n;
-    });
+    return guarded([&] { g_launches.read(count, reset); });
 }
 
 }   // extern "C"

@@ -89,8 +89,11 @@ def check_sums(x, off=0):
 # ---------------------------------------------------------------------------------------------------
 # channel sums
 # ---------------------------------------------------------------------------------------------------
+# (200, 2, 49): the flat path in two splits. n = 9800 a channel and two channels give
+# split_count = min(2048 / 2, ceil(9800 / 8192)) = 2 and chunk = ceil(4900 / 256) * 256 = 5120, so the
+# second split holds 4680 elements: `hi` clipped to n, and 4680 = 9 * 512 + 72 leaves lanes 0..71 an odd step.
 PLANAR = [(1, 1, 1), (2, 3, 49), (3, 5, 1), (2, 70, 15), (1, 300, 7), (4, 2, 3136), (2, 3, 12544),
-          (3, 4, 127), (3, 4, 128), (2, 2, 4097), (40, 3, 961)]
+          (3, 4, 127), (3, 4, 128), (2, 2, 4097), (40, 3, 961), (200, 2, 49), (32, 7, 196)]
 INTERLEAVED = [(1, 1), (5, 3), (3, 1000), (257, 130), (4096, 7), (64, 8), (700, 12), (9, 1028)]
 
 

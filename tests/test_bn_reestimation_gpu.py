@@ -159,10 +159,14 @@ def check_statistics(x, off=0):
 # ---------------------------------------------------------------------------------------------------
 # 1. statistics
 # ---------------------------------------------------------------------------------------------------
+# (200, 2, 49): the flat path in two splits. n = 9800 a channel and two channels give
+# split_count = min(2048 / 2, ceil(9800 / 8192)) = 2 and chunk = ceil(4900 / 256) * 256 = 5120, so the
+# second split holds 4680 elements: `hi` clipped to n, and 4680 = 9 * 512 + 72 leaves lanes 0..71 an odd step.
 PLANAR = [(1, 1, 2), (2, 3, 1), (2, 5, 49), (3, 4, 127), (3, 4, 128), (2, 2, 4097), (4, 3, 3136), (32, 7, 196),
-          (2, 70, 15), (1, 300, 7), (40, 3, 961)]
-INTERLEAVED = [(2, 1), (5, 3), (257, 130), (4096, 7), (64, 8), (9, 1028)]
-UNALIGNED = [(4, 3, 3136), (3, 4, 128), (2, 70, 15), (64, 8, 1)]
+          (2, 70, 15), (1, 300, 7), (40, 3, 961), (200, 2, 49)]
+# (3, 1000) and (700, 12): vector columns; (700, 12) has LX = 4 and two row splits
+INTERLEAVED = [(2, 1), (5, 3), (257, 130), (4096, 7), (64, 8), (9, 1028), (3, 1000), (700, 12)]
+UNALIGNED = [(4, 3, 3136), (3, 4, 128), (2, 70, 15), (64, 8, 1), (3, 1000, 1), (5, 3, 1)]
 ALL_SHAPES = PLANAR + [(r, c, 1) for r, c in INTERLEAVED]
 
 
