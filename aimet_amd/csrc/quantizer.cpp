@@ -81,7 +81,7 @@ void reset_device_state(aimet_tensor_quantizer* q, hipStream_t s)
         AIMET_HIP_CHECK(hipMemsetAsync(q->d.minmax, 0, sizeof(float) * 2 * q->C, s));
     if (q->d.counts && !in_arena(q, q->d.counts))
         AIMET_HIP_CHECK(hipMemsetAsync(q->d.counts, 0, sizeof(unsigned long long) * kPdfSize * q->C, s));
-    launch_reset_state(q->d, q->C, q->hist, s);
+    launch_reset_state(q->d, q->C, s);
 }
 
 void check_shape(aimet_tensor_quantizer* q, int64_t outer, int64_t C, int64_t K)

@@ -16,6 +16,9 @@
 //     updateStats call is 2-4 stream-ordered launches with no host synchronisation.
 //   * per-channel: all channels in one launch, one workgroup per channel.
 // Arithmetic follows the reference CPU code bit for bit (DTYPE = float; see common.hpp).
+//
+// The single-quantizer kernels and the batched ones over job tables (*_many) are two layers over
+// one set of device functions, each body written once (DESIGN.md §5 lists them).
 #include "entropy_core.hpp"
 #include "tq_state.hpp"
 
@@ -89,43 +92,54 @@ __device__ __forceinline__ void accum4(const float4& v, float& mn, float& mx)
     mx = fmaxf(fmaxf(mx, v.x), fmaxf(v.y, fmaxf(v.z, v.w)));
 }
 
+// ---- the two load bodies of every per-tensor min/max pass ------------------------------------
+// One round of streaming loads: 4 x 16 B nontemporal per lane, all in flight before the first
+// compare, at p[u * kBlock] (tools/studies/hist_variants.hip: 6.8 TB/s). Vector u exists when
+// at + u * kBlock < end; the others are padded with NaN, which fminf/fmaxf ignore. The grid-stride
+// loop passes (b, nvec), the tile (0, nvec - base): the guard in the form each compiles best
+// (profiles/r19/stats_isa.txt). A global-address-space pointer, so that a tensor whose address
+// came out of a job table is read with global_load, not flat_load.
+typedef const __attribute__((address_space(1))) f4* gf4p;
+
+__device__ __forceinline__ void minmax_round(gf4p p, int64_t at, int64_t end, float& mn, float& mx)
+{
+    f4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        v[u] = at + u * kBlock < end ? __builtin_nontemporal_load(p + u * kBlock) : f4 {NAN, NAN, NAN, NAN};
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+        accum4(make_float4(v[u].x, v[u].y, v[u].z, v[u].w), mn, mx);
+}
+
+// x[i], x[i + step], ... below `end`, one float at a time: tensors that are not 16-B aligned, and
+// the < 4 elements behind the last whole vector
+__device__ __forceinline__ void minmax_range(const float* __restrict__ x, int64_t i, int64_t end, int64_t step,
+                                             float& mn, float& mx)
+{
+    for (; i < end; i += step)
+    {
+        mn = fminf(mn, x[i]);
+        mx = fmaxf(mx, x[i]);
+    }
+}
+
 // ---- per-tensor min/max: partials[block] = {-min, max} --------------------------------------
-// One workgroup's share (block `blk` of `nblk`) of the min/max pass over x[0, n).
+// One workgroup's share (block `blk` of `nblk`) of the min/max pass over x[0, n): grid-stride rounds.
 __device__ __forceinline__ void minmax_part(const float* __restrict__ x, int64_t n, int vec, int64_t blk,
                                             int64_t nblk, float2* __restrict__ partials)
 {
     float mn = INFINITY, mx = -INFINITY;
     if (vec)
     {
-        // streaming 16-B loads, 4 in flight per lane (tools/studies/hist_variants.hip: 6.8 TB/s)
-        const f4* x4         = reinterpret_cast<const f4*>(x);
-        int64_t nvec         = n / 4;
+        const int64_t nvec   = n / 4;
         const int64_t stride = nblk * kBlock * 4;
         for (int64_t b = blk * kBlock * 4 + threadIdx.x; b < nvec; b += stride)
-        {
-            f4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)   // NaN padding is ignored by fminf/fmaxf
-                v[u] = b + u * kBlock < nvec ? __builtin_nontemporal_load(x4 + b + u * kBlock)
-                                             : f4 {NAN, NAN, NAN, NAN};
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                accum4(make_float4(v[u].x, v[u].y, v[u].z, v[u].w), mn, mx);
-        }
-        for (int64_t i = nvec * 4 + blk * kBlock + threadIdx.x; i < n; i += nblk * kBlock)
-        {
-            mn = fminf(mn, x[i]);
-            mx = fmaxf(mx, x[i]);
-        }
+            minmax_round((gf4p) x + b, b, nvec, mn, mx);
+        minmax_range(x, nvec * 4 + blk * kBlock + threadIdx.x, n, nblk * kBlock, mn, mx);
     }
     else
-    {
-        for (int64_t i = blk * kBlock + threadIdx.x; i < n; i += nblk * kBlock)
-        {
-            mn = fminf(mn, x[i]);
-            mx = fmaxf(mx, x[i]);
-        }
-    }
+        minmax_range(x, blk * kBlock + threadIdx.x, n, nblk * kBlock, mn, mx);
     block_minmax(mn, mx);
     if (threadIdx.x == 0)
         partials[blk] = make_float2(-mn, mx);
@@ -140,7 +154,32 @@ __global__ __launch_bounds__(kBlock) void minmax_tensor_kernel(const float* __re
     minmax_part(x, n, vec, blockIdx.x, gridDim.x, partials);
 }
 
-// Combine per-block partials {-min, max} into minmax[0].
+// One workgroup combines nb partials {-min, max} into one; the result is valid in thread 0. U loads
+// are in flight per lane: a 205-MB tensor leaves 12.5 K tile partials, which with U = 24 arrive in
+// two rounds of latency (8 per lane took ~22 us for ResNet-50's 55 quantizers, the critical path
+// between the two passes of a batched call); the <= kMinmaxParts partials of a single call take 1.
+template <int U>
+__device__ __forceinline__ float2 combine_partials(const float2* __restrict__ partials, uint32_t nb)
+{
+    float a = -INFINITY, b = -INFINITY;
+    for (uint32_t i0 = threadIdx.x; i0 < nb; i0 += kBlock * U)
+    {
+        float2 p[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            p[u] = i0 + u * kBlock < nb ? partials[i0 + u * kBlock] : make_float2(-INFINITY, -INFINITY);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+        {
+            a = fmaxf(a, p[u].x);
+            b = fmaxf(b, p[u].y);
+        }
+    }
+    float na = -a;            // min over -(partials.x) == global min
+    block_minmax(na, b);      // na: block min of mins, b: block max of maxes
+    return make_float2(-na, b);
+}
+
 __global__ __launch_bounds__(kBlock) void minmax_combine_max_kernel(const float2* __restrict__ partials, int nparts,
                                                                     float2* __restrict__ minmax,
                                                                     const int32_t* __restrict__ pdf_init,
@@ -148,19 +187,52 @@ __global__ __launch_bounds__(kBlock) void minmax_combine_max_kernel(const float2
 {
     if (skip_if_init && pdf_init[0])
         return;
-    float a = -INFINITY, b = -INFINITY;
-    for (int i = threadIdx.x; i < nparts; i += kBlock)
-    {
-        a = fmaxf(a, partials[i].x);
-        b = fmaxf(b, partials[i].y);
-    }
-    float na = -a;            // min over -(partials.x) == global min
-    block_minmax(na, b);      // na: block min of mins, b: block max of maxes
+    const float2 r = combine_partials<1>(partials, (uint32_t) nparts);
     if (threadIdx.x == 0)
-        minmax[0] = make_float2(-na, b);
+        minmax[0] = r;
 }
 
-// ---- per-channel min/max: one workgroup per channel of [outer][C][K] -----------------------
+// ---- per-channel passes: one workgroup per channel of [outer][C][K] --------------------------
+// The workgroup's walk over channel c, row by row: each4 takes a float4 of a 16-B aligned row (vec),
+// each1 one float of any other.
+template <class Each4, class Each1>
+__device__ __forceinline__ void channel_rows(const float* __restrict__ x, int64_t outer, int64_t C, int64_t K, int vec,
+                                             int64_t c, Each4 each4, Each1 each1)
+{
+    for (int64_t o = 0; o < outer; ++o)
+    {
+        const float* row = x + (o * C + c) * K;
+        if (vec)
+        {
+            const float4* r4 = reinterpret_cast<const float4*>(row);
+            for (int64_t k = threadIdx.x; k < K / 4; k += kBlock)
+            {
+                const float4 v = r4[k];   // a copy: one 16-B load (a functor given r4[k] itself read four floats)
+                each4(v);
+            }
+        }
+        else
+        {
+            for (int64_t k = threadIdx.x; k < K; k += kBlock)
+                each1(row[k]);
+        }
+    }
+}
+
+// every lane's share of channel c's min/max (block_minmax follows)
+__device__ __forceinline__ void channel_minmax(const float* __restrict__ x, int64_t outer, int64_t C, int64_t K,
+                                               int vec, int64_t c, float& mn, float& mx)
+{
+    mn = INFINITY;
+    mx = -INFINITY;
+    channel_rows(
+        x, outer, C, K, vec, c, [&](const float4& v) { accum4(v, mn, mx); },
+        [&](float v) {
+            mn = fminf(mn, v);
+            mx = fmaxf(mx, v);
+        });
+}
+
 __global__ __launch_bounds__(kBlock) void minmax_channel_kernel(const float* __restrict__ x, int64_t outer, int64_t C,
                                                                 int64_t K, int vec, float2* __restrict__ minmax,
                                                                 const int32_t* __restrict__ pdf_init,
@@ -170,25 +242,8 @@ __global__ __launch_bounds__(kBlock) void minmax_channel_kernel(const float* __r
     {
         if (skip_if_init && pdf_init[c])
             continue;
-        float mn = INFINITY, mx = -INFINITY;
-        for (int64_t o = 0; o < outer; ++o)
-        {
-            const float* row = x + (o * C + c) * K;
-            if (vec)
-            {
-                const float4* r4 = reinterpret_cast<const float4*>(row);
-                for (int64_t k = threadIdx.x; k < K / 4; k += kBlock)
-                    accum4(r4[k], mn, mx);
-            }
-            else
-            {
-                for (int64_t k = threadIdx.x; k < K; k += kBlock)
-                {
-                    mn = fminf(mn, row[k]);
-                    mx = fmaxf(mx, row[k]);
-                }
-            }
-        }
+        float mn, mx;
+        channel_minmax(x, outer, C, K, vec, c, mn, mx);
         block_minmax(mn, mx);
         if (threadIdx.x == 0)
             minmax[c] = make_float2(-mn, mx);
@@ -494,73 +549,78 @@ __global__ __launch_bounds__(BLOCK) void histogram_tensor_kernel(const float* __
     histogram_part<BLOCK, ENT, COLS>(x, n, vec, blockIdx.x, gridDim.x, d);
 }
 
-// per-channel: one workgroup per channel, counts written directly
+// per-channel: one workgroup per channel, one [512] LDS histogram per wave. The scan of channel c:
+// false (and nothing done) when the channel is not binned this batch; otherwise the waves'
+// histograms are complete behind its last barrier and hist_total(lds, b) is bin b's count. Exact
+// zeros are counted in a register and added once per wave.
+typedef uint32_t ChannelHist[kWaves][kPdfSize];
+
+template <bool ENT>
+__device__ __forceinline__ bool channel_hist_scan(ChannelHist& lds, const float* __restrict__ x, int64_t outer,
+                                                  int64_t C, int64_t K, int vec, const TqDevice& d, int64_t c)
+{
+    if (!BinnerOf<ENT>::live(d, c))
+        return false;
+    const int w = threadIdx.x >> 6;
+    typename BinnerOf<ENT>::type bn {d.bin_bucket[c], d.bin_offset[c]};
+    for (int i = threadIdx.x; i < kWaves * kPdfSize; i += kBlock)
+        (&lds[0][0])[i] = 0;
+    __syncthreads();
+    const int zbin = bn.bin(0.0f);
+    uint32_t zc    = 0;
+    auto add = [&](float v) {
+        if (v == 0.0f)
+        {
+            ++zc;
+            return;
+        }
+        int b = bn.bin(v);
+        if (b >= 0)
+            atomicAdd(&lds[w][b], 1u);
+    };
+    channel_rows(
+        x, outer, C, K, vec, c,
+        [&](const float4& v) {
+            add(v.x);
+            add(v.y);
+            add(v.z);
+            add(v.w);
+        },
+        add);
+    zc = wave_sum(zc);
+    if ((threadIdx.x & 63) == 0 && zbin >= 0 && zc)
+        atomicAdd(&lds[w][zbin], zc);
+    __syncthreads();
+    return true;
+}
+
+__device__ __forceinline__ uint32_t hist_total(const ChannelHist& lds, int b)
+{
+    uint32_t s = 0;
+#pragma unroll
+    for (int i = 0; i < kWaves; ++i)
+        s += lds[i][b];
+    return s;
+}
+
+// the single launch stores the totals (fold_histogram_kernel / ent_fold_histogram_kernel fold them)
 template <bool ENT>
 __global__ __launch_bounds__(kBlock) void histogram_channel_kernel(const float* __restrict__ x, int64_t outer,
                                                                    int64_t C, int64_t K, int vec, TqDevice d)
 {
-    __shared__ uint32_t lds[kWaves][kPdfSize];
-    const int w = threadIdx.x >> 6;
+    __shared__ ChannelHist lds;
     for (int64_t c = blockIdx.x; c < C; c += gridDim.x)
     {
-        if (!BinnerOf<ENT>::live(d, c))
+        if (!channel_hist_scan<ENT>(lds, x, outer, C, K, vec, d, c))
             continue;
-        typename BinnerOf<ENT>::type bn {d.bin_bucket[c], d.bin_offset[c]};
-        for (int i = threadIdx.x; i < kWaves * kPdfSize; i += kBlock)
-            (&lds[0][0])[i] = 0;
-        __syncthreads();
-        const int zbin = bn.bin(0.0f);
-        uint32_t zc    = 0;
-        auto add = [&](float v) {
-            if (v == 0.0f)
-            {
-                ++zc;
-                return;
-            }
-            int b = bn.bin(v);
-            if (b >= 0)
-                atomicAdd(&lds[w][b], 1u);
-        };
-        for (int64_t o = 0; o < outer; ++o)
-        {
-            const float* row = x + (o * C + c) * K;
-            if (vec)
-            {
-                const float4* r4 = reinterpret_cast<const float4*>(row);
-                for (int64_t k = threadIdx.x; k < K / 4; k += kBlock)
-                {
-                    float4 v = r4[k];
-                    add(v.x);
-                    add(v.y);
-                    add(v.z);
-                    add(v.w);
-                }
-            }
-            else
-            {
-                for (int64_t k = threadIdx.x; k < K; k += kBlock)
-                    add(row[k]);
-            }
-        }
-        zc = wave_sum(zc);
-        if ((threadIdx.x & 63) == 0 && zbin >= 0 && zc)
-            atomicAdd(&lds[w][zbin], zc);
-        __syncthreads();
         for (int b = threadIdx.x; b < kPdfSize; b += kBlock)
-        {
-            uint32_t s = 0;
-#pragma unroll
-            for (int i = 0; i < kWaves; ++i)
-                s += lds[i][b];
-            d.counts[c * kPdfSize + b] = s;
-        }
+            d.counts[c * kPdfSize + b] = hist_total(lds, b);
         __syncthreads();
     }
 }
 
-// UpdatePdf:277-287 -- pdf = (pdf * it + count / N) / (it + 1), double, per bin.
-// UpdatePdf:280-287 for channel c (one 512-lane workgroup): pdf = (pdf*it + cnt/N)/(it+1) in
-// double; counts cleared for the next batch
+// UpdatePdf:277-287 for channel c (one 512-lane workgroup): pdf = (pdf * it + count / N) / (it + 1)
+// in double, per bin; counts cleared for the next batch
 __device__ __forceinline__ void fold_hist_one(const TqDevice& d, int64_t c, int64_t count)
 {
     int it        = d.iterations[c];
@@ -593,14 +653,19 @@ __global__ __launch_bounds__(kPdfSize) void ent_fold_histogram_kernel(TqDevice d
             ent_fold_hist_one(d, c);
 }
 
+// the TF accumulator of channel c back to "nothing seen"
+__device__ __forceinline__ void reset_acc_one(double* acc, int64_t c)
+{
+    acc[2 * c]     = DBL_MAX;    // TfEncodingAnalyzer.h:88
+    acc[2 * c + 1] = -DBL_MAX;   // TfEncodingAnalyzer.h:89
+}
+
+// one lane per channel
 __global__ __launch_bounds__(kBlock) void reset_acc_kernel(double* acc, int64_t C)
 {
     int64_t c = (int64_t) blockIdx.x * kBlock + threadIdx.x;
     if (c < C)
-    {
-        acc[2 * c]     = DBL_MAX;    // TfEncodingAnalyzer.h:88
-        acc[2 * c + 1] = -DBL_MAX;   // TfEncodingAnalyzer.h:89
-    }
+        reset_acc_one(acc, c);
 }
 
 // one workgroup per quantizer
@@ -608,10 +673,7 @@ __global__ __launch_bounds__(kBlock) void reset_acc_many_kernel(const ResetJob* 
 {
     const ResetJob J = jobs[blockIdx.x];
     for (int64_t c = threadIdx.x; c < J.C; c += kBlock)
-    {
-        J.acc[2 * c]     = DBL_MAX;    // TfEncodingAnalyzer.h:88
-        J.acc[2 * c + 1] = -DBL_MAX;   // TfEncodingAnalyzer.h:89
-    }
+        reset_acc_one(J.acc, c);
 }
 
 // ---- many per-tensor quantizers in one launch per phase ---------------------------------------
@@ -654,51 +716,42 @@ __device__ __forceinline__ int find_job(const StatsJob* __restrict__ jobs, int n
 // at once (ViT-L/16 calibration: 900 -> 1016 Gelem/s; profiles/r02/compute_encodings_study.txt).
 constexpr int64_t kMmTile = (int64_t) kBlock * 16;   // elements per tile
 constexpr int kMmGrid     = 2048;                    // 256 CUs x 8 workgroups of 256 lanes
-typedef const __attribute__((address_space(1))) f4* gf4p;
 
+// tile `tile` of x[0, n): one round of loads; the result is valid in thread 0
 __device__ __forceinline__ float2 minmax_tile(const float* __restrict__ x, int64_t n, int vec, int64_t tile,
                                               bool last_tile)
 {
     float mn = INFINITY, mx = -INFINITY;
     if (vec)
     {
-        gf4p x4            = (gf4p) x;
         const int64_t nvec = n / 4;
         const int64_t base = tile * (kMmTile / 4) + threadIdx.x;
-        f4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)   // NaN padding is ignored by fminf/fmaxf
-            v[u] = base + u * kBlock < nvec ? __builtin_nontemporal_load(x4 + base + u * kBlock)
-                                            : f4 {NAN, NAN, NAN, NAN};
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            accum4(make_float4(v[u].x, v[u].y, v[u].z, v[u].w), mn, mx);
+        minmax_round((gf4p) x + base, 0, nvec - base, mn, mx);
         if (last_tile)   // the last tile also takes the < 4 trailing elements
-            for (int64_t i = nvec * 4 + threadIdx.x; i < n; i += kBlock)
-            {
-                mn = fminf(mn, x[i]);
-                mx = fmaxf(mx, x[i]);
-            }
+            minmax_range(x, nvec * 4 + threadIdx.x, n, kBlock, mn, mx);
     }
     else
     {
         const int64_t end = (tile + 1) * kMmTile < n ? (tile + 1) * kMmTile : n;
-        for (int64_t i = tile * kMmTile + threadIdx.x; i < end; i += kBlock)
-        {
-            mn = fminf(mn, x[i]);
-            mx = fmaxf(mx, x[i]);
-        }
+        minmax_range(x, tile * kMmTile + threadIdx.x, end, kBlock, mn, mx);
     }
     block_minmax(mn, mx);   // ends with the result in thread 0 (and an LDS barrier inside)
     return make_float2(-mn, mx);
+}
+
+// PDF schemes take min/max on the first (non-zero) batch only: once the range is fixed, the min/max
+// pass and its combine skip the job. `fresh`: see StatsJob.
+__device__ __forceinline__ bool range_fixed(const StatsJob* J)
+{
+    return J->hist && !J->ent && !J->fresh && J->d.pdf_init[0];
 }
 
 // one tile per workgroup (the first batch: every tile is read)
 __global__ __launch_bounds__(kBlock) void minmax_many_kernel(const StatsJob* __restrict__ jobs, int njobs)
 {
     const StatsJob& J = jobs[find_job(jobs, njobs, blockIdx.x, false)];
-    if (J.hist && !J.ent && !J.fresh && J.d.pdf_init[0])
-        return;   // PDF schemes take min/max on the first (non-zero) batch only
+    if (range_fixed(&J))
+        return;
     const int64_t tile = blockIdx.x - J.mm_block0;
     const float2 r     = minmax_tile(J.x, J.n, J.vec, tile, tile + 1 == (int64_t) J.mm_blocks);
     if (threadIdx.x == 0)
@@ -730,8 +783,7 @@ __global__ __launch_bounds__(kBlock) void minmax_walk_kernel(const StatsJob* __r
         part    = reinterpret_cast<float2*>(J.mm_part);
         b0      = J.mm_block0;
         next_b0 = j + 1 < njobs ? jobs[j + 1].mm_block0 : tiles;
-        // PDF schemes take min/max on the first (non-zero) batch only
-        skip = J.hist && !J.ent && !J.fresh && J.d.pdf_init[0];
+        skip    = range_fixed(&J);
     };
     // the first quantizer after `from` that is not skipped (njobs if none): 64 job entries per
     // round of parallel loads, instead of one dependent load per skipped quantizer (a later ViT-L/16
@@ -741,12 +793,7 @@ __global__ __launch_bounds__(kBlock) void minmax_walk_kernel(const StatsJob* __r
         for (int base = from; base < njobs; base += 64)
         {
             const int j = base + lane;
-            bool live   = false;
-            if (j < njobs)
-            {
-                const StatsJob& J = jobs[j];
-                live              = !(J.hist && !J.ent && !J.fresh && J.d.pdf_init[0]);
-            }
+            const bool live            = j < njobs && !range_fixed(jobs + j);
             const unsigned long long m = __ballot(live);
             if (m)
                 return base + (int) __builtin_ctzll(m);
@@ -786,34 +833,13 @@ __global__ __launch_bounds__(kBlock) void combine_many_kernel(const StatsJob* __
     const StatsJob& J = jobs[blockIdx.x];
     if (J.count_out && threadIdx.x == 0)
         *J.count_out = J.n;   // this rank's element count, summed over ranks with the bin counts
-    if (J.hist && !J.ent && !J.fresh && J.d.pdf_init[0])
+    if (range_fixed(&J))
         return;
-    const float2* partials = reinterpret_cast<const float2*>(J.mm_part);
-    float a = -INFINITY, b = -INFINITY;
-    // a 205-MB tensor leaves 12.5 K tile partials: 24 independent loads in flight per lane, so the
-    // largest quantizer's partials arrive in two rounds of latency (8 per lane took ~22 us for
-    // ResNet-50's 55 quantizers, the call's critical path between the two passes)
-    constexpr int kU  = 24;
-    const uint32_t nb = J.mm_blocks;
-    for (uint32_t i0 = threadIdx.x; i0 < nb; i0 += kBlock * kU)
-    {
-        float2 p[kU];
-#pragma unroll
-        for (int u = 0; u < kU; ++u)
-            p[u] = i0 + u * kBlock < nb ? partials[i0 + u * kBlock] : make_float2(-INFINITY, -INFINITY);
-#pragma unroll
-        for (int u = 0; u < kU; ++u)
-        {
-            a = fmaxf(a, p[u].x);
-            b = fmaxf(b, p[u].y);
-        }
-    }
-    float na = -a;
-    block_minmax(na, b);
+    const float2 r = combine_partials<24>(reinterpret_cast<const float2*>(J.mm_part), J.mm_blocks);
     __shared__ float2 res;
     if (threadIdx.x == 0)
     {
-        res = make_float2(-na, b);
+        res = r;
         reinterpret_cast<float2*>(J.d.minmax)[0] = res;
         if (fold && !J.ent)
             fold_one(J.d, 0, !J.hist);
@@ -876,30 +902,6 @@ __device__ __forceinline__ int find_channel_job(const ChannelJob* __restrict__ j
     return find_job_ballot(jobs, njobs, b, [](const ChannelJob& j) { return j.block0; });
 }
 
-__device__ __forceinline__ void channel_minmax(const ChannelJob& J, int64_t c, float& mn, float& mx)
-{
-    mn = INFINITY;
-    mx = -INFINITY;
-    for (int64_t o = 0; o < J.outer; ++o)
-    {
-        const float* row = J.x + (o * J.C + c) * J.K;
-        if (J.vec)
-        {
-            const float4* r4 = reinterpret_cast<const float4*>(row);
-            for (int64_t k = threadIdx.x; k < J.K / 4; k += kBlock)
-                accum4(r4[k], mn, mx);
-        }
-        else
-        {
-            for (int64_t k = threadIdx.x; k < J.K; k += kBlock)
-            {
-                mn = fminf(mn, row[k]);
-                mx = fmaxf(mx, row[k]);
-            }
-        }
-    }
-}
-
 // min/max of channel c + fold_one / ent_fold_one (fold_minmax_kernel, ent_fold_minmax_kernel)
 __global__ __launch_bounds__(kBlock) void channel_minmax_fold_many_kernel(const ChannelJob* __restrict__ jobs,
                                                                           int njobs)
@@ -909,7 +911,7 @@ __global__ __launch_bounds__(kBlock) void channel_minmax_fold_many_kernel(const 
     if (J.kind == kKindPdf && J.d.pdf_init[c])
         return;   // PDF schemes take min/max on the first (non-zero) batch only
     float mn, mx;
-    channel_minmax(J, c, mn, mx);
+    channel_minmax(J.x, J.outer, J.C, J.K, J.vec, c, mn, mx);
     block_minmax(mn, mx);
     __shared__ float2 res;
     if (threadIdx.x == 0)
@@ -931,60 +933,15 @@ __global__ __launch_bounds__(kBlock) void channel_minmax_fold_many_kernel(const 
 template <bool ENT>
 __device__ __forceinline__ void channel_hist_fold(const ChannelJob& J, int64_t c)
 {
-    __shared__ uint32_t lds[kWaves][kPdfSize];
+    __shared__ ChannelHist lds;
     const TqDevice& d = J.d;
-    if (!BinnerOf<ENT>::live(d, c))
+    if (!channel_hist_scan<ENT>(lds, J.x, J.outer, J.C, J.K, J.vec, d, c))
         return;
-    const int w = threadIdx.x >> 6;
-    typename BinnerOf<ENT>::type bn {d.bin_bucket[c], d.bin_offset[c]};
-    for (int i = threadIdx.x; i < kWaves * kPdfSize; i += kBlock)
-        (&lds[0][0])[i] = 0;
-    __syncthreads();
-    const int zbin = bn.bin(0.0f);
-    uint32_t zc    = 0;
-    auto add = [&](float v) {
-        if (v == 0.0f)
-        {
-            ++zc;
-            return;
-        }
-        int b = bn.bin(v);
-        if (b >= 0)
-            atomicAdd(&lds[w][b], 1u);
-    };
-    for (int64_t o = 0; o < J.outer; ++o)
-    {
-        const float* row = J.x + (o * J.C + c) * J.K;
-        if (J.vec)
-        {
-            const float4* r4 = reinterpret_cast<const float4*>(row);
-            for (int64_t k = threadIdx.x; k < J.K / 4; k += kBlock)
-            {
-                float4 v = r4[k];
-                add(v.x);
-                add(v.y);
-                add(v.z);
-                add(v.w);
-            }
-        }
-        else
-        {
-            for (int64_t k = threadIdx.x; k < J.K; k += kBlock)
-                add(row[k]);
-        }
-    }
-    zc = wave_sum(zc);
-    if ((threadIdx.x & 63) == 0 && zbin >= 0 && zc)
-        atomicAdd(&lds[w][zbin], zc);
-    __syncthreads();
     const int it       = d.iterations[c];
     const double count = (double) (J.outer * J.K);
     for (int b = threadIdx.x; b < kPdfSize; b += kBlock)
     {
-        uint32_t s = 0;
-#pragma unroll
-        for (int i = 0; i < kWaves; ++i)
-            s += lds[i][b];
+        const uint32_t s  = hist_total(lds, b);
         const int64_t idx = c * kPdfSize + b;
         if (ENT)
             d.pdf[idx] = d.pdf[idx] + (double) s;                        // math_functions.cpp:554-559
@@ -1176,13 +1133,36 @@ void launch_stats_table(const StatsJob* dj, int n, uint64_t mm, uint64_t hb, boo
     }
 }
 
+// The host side of every *_many wrapper: upload the job table, run the caller's launches over the
+// device copy, release the table -- and `extra`, a scratch block those launches use (or nullptr) --
+// on s, behind the launches. Both are released when the upload or a launch check throws, too.
+template <class Job, class Launches>
+static void with_job_table(const std::vector<Job>& jobs, void* extra, hipStream_t s, Launches launches)
+{
+    Job* dj      = nullptr;
+    auto release = [&]() {
+        scratch_free(extra, s);
+        scratch_free(dj, s);
+    };
+    try
+    {
+        dj = static_cast<Job*>(upload_async(jobs.data(), sizeof(Job) * jobs.size(), s));
+        launches(dj, (int) jobs.size());
+    }
+    catch (...)
+    {
+        release();
+        throw;
+    }
+    release();
+}
+
 void launch_stats_many(std::vector<StatsJob>& jobs, int phases, hipStream_t s, const std::function<void()>& between)
 {
     if (jobs.empty())
         return;
     uint64_t mm = 0, hb = 0;
     stats_layout(jobs, &mm, &hb);
-    const int n = (int) jobs.size();
     float* parts = nullptr;
     if (phases & kPhaseMinmax)
     {
@@ -1190,21 +1170,9 @@ void launch_stats_many(std::vector<StatsJob>& jobs, int phases, hipStream_t s, c
         for (auto& j: jobs)
             j.mm_part = parts + 2 * (int64_t) j.mm_block0;
     }
-    auto* dj = static_cast<StatsJob*>(upload_async(jobs.data(), sizeof(StatsJob) * n, s));
-    try
-    {
+    with_job_table(jobs, parts, s, [&](const StatsJob* dj, int n) {
         launch_stats_table(dj, n, mm, hb, stats_walk(jobs.data(), n), phases, s, between);
-    }
-    catch (...)
-    {
-        if (parts)
-            scratch_free(parts, s);
-        scratch_free(dj, s);
-        throw;
-    }
-    if (parts)
-        scratch_free(parts, s);
-    scratch_free(dj, s);
+    });
 }
 
 uint64_t channel_layout(std::vector<ChannelJob>& jobs, bool* any_hist)
@@ -1241,10 +1209,8 @@ void launch_channel_stats_many(std::vector<ChannelJob>& jobs, hipStream_t s)
         return;
     bool any_hist         = false;
     const uint64_t blocks = channel_layout(jobs, &any_hist);
-    const int n           = (int) jobs.size();
-    auto* dj              = static_cast<ChannelJob*>(upload_async(jobs.data(), sizeof(ChannelJob) * n, s));
-    launch_channel_table(dj, n, blocks, any_hist, s);
-    scratch_free(dj, s);
+    with_job_table(jobs, nullptr, s,
+                   [&](const ChannelJob* dj, int n) { launch_channel_table(dj, n, blocks, any_hist, s); });
 }
 
 void launch_reset_table(const ResetJob* dj, int n, hipStream_t s)
@@ -1259,9 +1225,7 @@ void launch_reset_state_many(const std::vector<ResetJob>& jobs, hipStream_t s)
 {
     if (jobs.empty())
         return;
-    auto* dj = static_cast<ResetJob*>(upload_async(jobs.data(), sizeof(ResetJob) * jobs.size(), s));
-    launch_reset_table(dj, (int) jobs.size(), s);
-    scratch_free(dj, s);
+    with_job_table(jobs, nullptr, s, [&](const ResetJob* dj, int n) { launch_reset_table(dj, n, s); });
 }
 
 // blockIdx.y = job; the workgroups along x stride over the job's 16-B words, then its tail bytes
@@ -1306,14 +1270,11 @@ void launch_zero_many(const std::vector<ZeroJob>& jobs, hipStream_t s)
     int64_t most = 0;
     for (const ZeroJob& j: jobs)
         most = std::max(most, j.bytes);
-    auto* dj = static_cast<ZeroJob*>(upload_async(jobs.data(), sizeof(ZeroJob) * jobs.size(), s));
-    launch_zero_table(dj, (int) jobs.size(), most, s);
-    scratch_free(dj, s);
+    with_job_table(jobs, nullptr, s, [&](const ZeroJob* dj, int n) { launch_zero_table(dj, n, most, s); });
 }
 
-void launch_reset_state(const TqDevice& d, int64_t C, bool hist, hipStream_t s)
+void launch_reset_state(const TqDevice& d, int64_t C, hipStream_t s)
 {
-    (void) hist;
     reset_acc_kernel<<<(int) ceil_div(C, kBlock), kBlock, 0, s>>>(d.acc, C);
     AIMET_LAUNCH_CHECK();
 }

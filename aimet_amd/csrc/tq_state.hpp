@@ -58,7 +58,7 @@ void launch_fold_minmax(const TqDevice& d, int64_t C, StatsKind kind, hipStream_
 void launch_batch_histogram(const TqDevice& d, const float* x, int64_t outer, int64_t C, int64_t K, StatsKind kind,
                             hipStream_t s);
 void launch_fold_histogram(const TqDevice& d, int64_t C, int64_t count, StatsKind kind, hipStream_t s);
-void launch_reset_state(const TqDevice& d, int64_t C, bool hist, hipStream_t s);
+void launch_reset_state(const TqDevice& d, int64_t C, hipStream_t s);
 // the TF accumulators of many quantizers (aimet_tq_create_many) in one launch
 struct ResetJob
 {

@@ -1045,6 +1045,111 @@ def test_update_stats_channels_many_equals_individual():
                 assert qa.getStatsHistogram(c) == qb.getStatsHistogram(c)
 
 
+@pytest.mark.parametrize("scheme", [QuantizationMode.QUANTIZATION_TF, QuantizationMode.QUANTIZATION_TF_ENHANCED])
+@pytest.mark.parametrize("K,offset", [(5, 1), (8, 0)])   # scalar rows of a 4-byte offset view / 16-B vector rows
+def test_per_channel_stats_past_the_grid_cap(scheme, K, offset):
+    """More channels than the 65536 workgroups of a single per-channel launch: updateStatsPerChannel
+    then loops over channels inside a workgroup (barriers in the loop), updateStatsPerChannelMany
+    runs one workgroup per channel. Two batches, an all-zero channel, the tensor's extreme values
+    in a channel past the cap: bit-identical TF encodings of every channel and histograms of
+    channels on both sides of the cap, and those channels equal to the CPU oracle."""
+    rng = np.random.default_rng(65536 + K)
+    C = 65536 + 3
+    probe = (0, 1, 65535, 65536, C - 1)
+    single, many = (AimetTensorQuantizer(scheme, num_channels=C) for _ in range(2))
+    orcs = {c: O.Analyzer(int(scheme)) for c in probe}
+    for batch in range(2):
+        x = (rng.standard_normal((C, K)) * (1 + batch)).astype(np.float32)
+        x[1] = 0.0
+        x[65537] *= 100.0
+        x[65537, :2] = -900.0 * (1 + batch), 1000.0 * (1 + batch)
+        t = gpu(np.concatenate([np.zeros(offset, np.float32), x.ravel()]))[offset:].view(C, K)
+        assert t.data_ptr() % 16 == 4 * offset
+        single.updateStatsPerChannel(t, 0, True)
+        keep = AimetTensorQuantizer.updateStatsPerChannelMany([many], [t], [0])
+        torch.cuda.synchronize()
+        del keep
+        for c, o in orcs.items():
+            o.update(x[c])
+    if scheme == QuantizationMode.QUANTIZATION_TF:
+        es, vs = single.getEncoding(8, False, False, False)
+        em, vm = many.getEncoding(8, False, False, False)
+        assert vs and vm
+        ts = np.array([e.to_tuple() for e in es], np.float64)
+        tm = np.array([e.to_tuple() for e in em], np.float64)
+        assert np.array_equal(ts.view(np.uint64), tm.view(np.uint64))
+        for c, o in orcs.items():
+            assert es[c].to_tuple() == o.compute(8).as_tuple(), c
+    else:
+        for c, o in orcs.items():
+            hs = single.getStatsHistogram(c)
+            assert hs == many.getStatsHistogram(c), c
+            xl, pdf = o.histogram()
+            assert hs == list(zip(xl.tolist(), pdf.tolist())), c
+
+
+def test_update_stats_many_entropy_equals_individual():
+    """The entropy analyzer in aimet_tq_update_stats_many == updateStats per quantizer: 1, 1000 and
+    65536 + 1 elements, three batches of which the second is wider than the first (the 512 bins
+    are redistributed) and, for every other quantizer, the first is all zero; the
+    TensorProfilingParams state and the encodings bit-identical."""
+    rng = np.random.default_rng(77)
+    sizes = [1, 1000, 65536 + 1] * 2
+    a = [AimetTensorQuantizer(QuantizationMode.QUANTIZATION_ENTROPY) for _ in sizes]
+    b = [AimetTensorQuantizer(QuantizationMode.QUANTIZATION_ENTROPY) for _ in sizes]
+    for batch, scale in enumerate((1.0, 4.0, 2.0)):
+        ts = []
+        for i, n in enumerate(sizes):
+            x = (rng.standard_normal(n + 1) * scale + 0.25).astype(np.float32)
+            if batch == 0 and i >= 3:
+                x[:] = 0.0
+            ts.append(gpu(x)[1:] if i % 2 else gpu(x[1:]))   # odd: a 4-byte offset view (scalar path)
+        AimetTensorQuantizer.updateStatsMany(a, ts)
+        for q, t in zip(b, ts):
+            q.updateStats(t, True)
+        torch.cuda.synchronize()
+    for i, (qa, qb) in enumerate(zip(a, b)):
+        sa, sb = qa.entropy_state(0), qb.entropy_state(0)
+        assert sa.keys() == sb.keys()
+        assert all(np.array_equal(np.asarray(sa[k]), np.asarray(sb[k])) for k in sa), i
+        assert sa["has_hist"] and sa["iterations"] == (2 if i >= 3 else 3), i
+        for fl in FLAGS:
+            ea, va = qa.getEncoding(8, *fl)
+            eb, vb = qb.getEncoding(8, *fl)
+            assert va == vb
+            ta, tb = np.array(ea.to_tuple(), np.float64), np.array(eb.to_tuple(), np.float64)
+            assert np.array_equal(ta.view(np.uint64), tb.view(np.uint64)), (i, fl)
+
+
+def test_update_stats_many_walk_with_fixed_and_unset_ranges():
+    """70 TF-Enhanced quantizers (> 64: the min/max pass walks the tiles from the first batch) of 1,
+    4097 and 3 tiles + 5 elements, every other one a 4-byte offset view. Quantizers 0, 33 and 69
+    see an all-zero first batch, so on the second their range is still unset between runs of
+    fixed ones (the walk skips to the next unset quantizer). Three batches through
+    updateStatsMany == updateStats each: histograms and encodings bit-identical."""
+    rng = np.random.default_rng(70)
+    tile = 256 * 16   # kMmTile, stats.hip
+    sizes = [(1, 4097, 3 * tile + 5)[i % 3] for i in range(70)]
+    a = [AimetTensorQuantizer(QuantizationMode.QUANTIZATION_TF_ENHANCED) for _ in sizes]
+    b = [AimetTensorQuantizer(QuantizationMode.QUANTIZATION_TF_ENHANCED) for _ in sizes]
+    for batch in range(3):
+        ts = []
+        for i, n in enumerate(sizes):
+            x = (rng.standard_normal(n + 1) * (1 + batch + i % 4) - 0.5).astype(np.float32)
+            if batch == 0 and i in (0, 33, 69):
+                x[:] = 0.0
+            ts.append(gpu(x)[1:] if i % 2 else gpu(x[1:]))
+        AimetTensorQuantizer.updateStatsMany(a, ts)
+        for q, t in zip(b, ts):
+            q.updateStats(t, True)
+        torch.cuda.synchronize()
+    for i, (qa, qb) in enumerate(zip(a, b)):
+        ha = qa.getStatsHistogram()
+        assert len(ha) == 512 and ha == qb.getStatsHistogram(), i
+        for fl in FLAGS:
+            assert qa.getEncoding(8, *fl)[0].to_tuple() == qb.getEncoding(8, *fl)[0].to_tuple(), (i, fl)
+
+
 def test_reset_many_then_recompute_equals_fresh_quantizers():
     """aimet_tq_reset_encoding_stats_many (one zeroing launch + one re-initialisation, no sync)
     leaves quantizers that calibrate exactly like new ones (TF, TF-E, percentile, MSE, entropy;

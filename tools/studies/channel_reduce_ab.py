@@ -35,15 +35,51 @@ RESIDENT_MAX_N = 15872
 STREAMING, RESIDENT = 1, 2
 
 
-def load(path):
+def load(path, prefixes=("aimet_bc_", "aimet_bnre_")):
     from aimet_amd import _native
     lib = ctypes.CDLL(path)
     for name, args in _native._PROTOTYPES.items():
-        if name.startswith(("aimet_bc_", "aimet_bnre_")):
+        if name.startswith(prefixes):
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = args, ctypes.c_int
     lib.aimet_last_error.restype = ctypes.c_char_p
     return lib
+
+
+def ok(lib, rc):
+    if rc != 0:
+        raise RuntimeError(lib.aimet_last_error().decode())
+
+
+def alternate(libs, stream, name, nbytes, launch, bad):
+    """The timing rule: launch(lib, i) is one call on input copy i; the libraries of `libs` ("parent", "new")
+    alternate, ROUNDS rounds after one warm round. A row that is slower is appended to `bad`."""
+    times = {"parent": [], "new": []}
+    turn = 0
+    for rnd in range(ROUNDS + 1):
+        for tag, lib in libs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(LAUNCHES):
+                launch(lib, turn)
+                turn += 1
+            e1.record(stream)
+            e1.synchronize()
+            if rnd > 0:
+                times[tag].append(e0.elapsed_time(e1) / LAUNCHES)
+    print(name)
+    med = {}
+    for tag in ("parent", "new"):
+        t = times[tag]
+        med[tag] = statistics.median(t)
+        print("  %-7s %s  median %.4f ms  %.1f GB/s  spread %.4f" % (
+            tag, " ".join("%.4f" % v for v in t), med[tag], nbytes / (med[tag] * 1e-3) / 1e9, max(t) - min(t)))
+    spread = max(times["parent"]) - min(times["parent"])
+    verdict = "ok" if med["new"] <= med["parent"] + spread else "SLOWER"
+    if verdict != "ok":
+        bad.append(name)
+    print("  new - parent = %+.4f ms (%+.2f %%), parent spread %.4f: %s\n" % (
+        med["new"] - med["parent"], 100 * (med["new"] - med["parent"]) / med["parent"], spread, verdict), flush=True)
 
 
 def sequential_sums(v):
@@ -86,10 +122,6 @@ def main():
     sp = ctypes.c_void_p(stream.cuda_stream)
     P = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
     bad = []
-
-    def ok(lib, rc):
-        if rc != 0:
-            raise RuntimeError(lib.aimet_last_error().decode())
 
     def set_form(form):
         for lib in libs.values():
@@ -169,35 +201,8 @@ def main():
     gen = torch.Generator(device=dev).manual_seed(0)
 
     def ab(name, nbytes, launch):
-        """launch(lib, i): one call on input copy i."""
-        if args.only not in name:
-            return
-        times = {"parent": [], "new": []}
-        turn = 0
-        for rnd in range(ROUNDS + 1):
-            for tag, lib in libs.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                for _ in range(LAUNCHES):
-                    launch(lib, turn)
-                    turn += 1
-                e1.record(stream)
-                e1.synchronize()
-                if rnd > 0:
-                    times[tag].append(e0.elapsed_time(e1) / LAUNCHES)
-        print(name)
-        med = {}
-        for tag in ("parent", "new"):
-            t = times[tag]
-            med[tag] = statistics.median(t)
-            print("  %-7s %s  median %.4f ms  %.1f GB/s  spread %.4f" % (
-                tag, " ".join("%.4f" % v for v in t), med[tag], nbytes / (med[tag] * 1e-3) / 1e9, max(t) - min(t)))
-        spread = max(times["parent"]) - min(times["parent"])
-        verdict = "ok" if med["new"] <= med["parent"] + spread else "SLOWER"
-        if verdict != "ok":
-            bad.append(name)
-        print("  new - parent = %+.4f ms (%+.2f %%), parent spread %.4f: %s\n" % (
-            med["new"] - med["parent"], 100 * (med["new"] - med["parent"]) / med["parent"], spread, verdict), flush=True)
+        if args.only in name:
+            alternate(libs, stream, name, nbytes, launch, bad)
 
     def copies_of(shape):
         """[copies][numel] random floats, every copy 16-byte aligned"""
