@@ -6,6 +6,7 @@ annealing). Here the forward is one kernel (W, alpha -> Wq) and the backward one
 (grad_Wq, W, alpha -> grad_alpha) that also folds in the rounding-loss gradient and value.
 """
 import math
+import struct
 
 import torch
 
@@ -16,12 +17,48 @@ ZETA = 1.1     # aimet_common/defs.py:305
 GAMMA = -0.1   # aimet_common/defs.py:304
 
 
+# the exponents on which the default (fast) pow is proven within 1 ulp of the correctly rounded
+# power: 0 (an exact case) and this interval (include/aimet_amd.h: AIMET_ADAROUND_FAST_POW_MIN_EXP /
+# _MAX_EXP; csrc/fast_pow.hpp; profiles/r20/adaround_pow_domain.txt)
+FAST_POW_EXPONENTS = (2.0 ** -10, 64.0)
+
+
+def _f32(v):
+    return struct.unpack("f", struct.pack("f", v))[0]
+
+
+def fast_pow_covers(beta) -> bool:
+    """Both exponents of one launch, beta and beta - 1 as the kernels read them (float32, the
+    difference formed in double), lie where the fast pow is proven."""
+    lo, hi = FAST_POW_EXPONENTS
+    return all(e == 0.0 or lo <= e <= hi for e in (_f32(float(beta)), _f32(float(beta) - 1.0)))
+
+
+def exact_pow_needed(beta_range) -> bool:
+    """Whether a loop annealing beta between the two ends of `beta_range` (monotone, compute_beta)
+    leaves the fast pow's proven exponents and has to run with the exact pow. Raises ValueError
+    for an end below 1: beta - 1 < 0 is a negative exponent, where neither pow form follows
+    torch's at |2h - 1| = 0 (inf there, NaN after abs' backward)."""
+    lo, hi = sorted(float(b) for b in beta_range)
+    if not lo >= 1.0 or not math.isfinite(hi):
+        raise ValueError("AdaRound: beta_range %r is not supported: both ends must be finite and at least 1 "
+                         "(the rounding loss's gradient takes |2h - 1|^(beta - 1))" % (tuple(beta_range),))
+    if lo == hi:
+        return not fast_pow_covers(lo)
+    # every beta in between occurs: the interval has to be covered, not only its ends
+    return not (_f32(lo - 1.0) >= FAST_POW_EXPONENTS[0] and fast_pow_covers(lo) and fast_pow_covers(hi))
+
+
 def set_exact_pow(exact: bool):
     """The rounding loss's pow for every AdaRound backward launched afterwards (process-wide,
-    aimet_adaround_set_exact_pow): False (default) the table-driven f32 pow, within 1 ulp of torch's CPU pow
-    (Sleef powf_u10) over every f32 input in (0, 1) and the AdaRound beta schedules
-    (profiles/r06/pow_fast_check.txt); True the bit-exact emulation of torch's pow, about 3x the
-    arithmetic. Returns the previous setting."""
+    aimet_adaround_set_exact_pow): False (default) the table-driven f32 pow, within 1 ulp of the
+    correctly rounded power -- and so of torch's CPU pow (Sleef powf_u10) -- for exponents beta and
+    beta - 1 that are 0 or lie in FAST_POW_EXPONENTS (tests/test_adaround_pow_domain_gpu.py against
+    a float64 reference, profiles/r20/adaround_pow_domain.txt; every f32 input in (0, 1) against the
+    Sleef emulation on the default schedules, profiles/r06/pow_fast_check.txt); True the bit-exact
+    emulation of torch's pow, about 3x the arithmetic. A launch with a host-side beta outside those
+    exponents takes the exact form by itself; AdaroundOptimizer selects it for a layer's loop
+    whose beta_range leaves them (exact_pow_needed). Returns the previous setting."""
     prev = get_exact_pow()
     _native.call("aimet_adaround_set_exact_pow", int(bool(exact)))
     return prev

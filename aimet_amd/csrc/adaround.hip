@@ -775,6 +775,14 @@ bool exact_pow()
     return exact_pow_flag().load(std::memory_order_relaxed) != 0;
 }
 
+// the exponents on which the fast pow is proven (fast_pow.hpp; AIMET_ADAROUND_FAST_POW_*): the
+// exact case 0, or [2^-10, 64]; both of a launch's exponents, beta and beta - 1, as the kernels
+// read them (float32)
+bool fast_pow_covers(float e)
+{
+    return e == 0.0f || (e >= AIMET_ADAROUND_FAST_POW_MIN_EXP && e <= AIMET_ADAROUND_FAST_POW_MAX_EXP);
+}
+
 // ---- one optimizer step fused into the backward (single-process HIP-graph loop) -----------------
 // torch.optim.Adam(fused=True) per element, as ATen's adam_math (native/hip/fused_adam_utils.cuh)
 // computes it for a float parameter without weight decay / amsgrad / maximize: the moments in
@@ -1237,6 +1245,14 @@ int adaround_backward(const float* w, const float* alpha, const float* g, float*
             round_loss = nullptr;
         AdaParams p {(float) ((1ull << bw) - 1), (float) reg, (float) beta, (float) (beta - 1.0), 1,
                      (uint32_t) (n - n % 32), round_loss != nullptr};
+        // a host-side exponent: below beta = 1 the gradient's exponent is negative, where neither pow
+        // form follows torch at |2h - 1| = 0 (inf there, NaN after abs' backward): refused; outside
+        // the fast pow's proven exponents this launch takes the exact form (device-resident
+        // exponents: the caller's precondition, aimet_amd.h)
+        const bool with_loss = !reg_beta && p.reg != 0.0f;
+        AIMET_REQUIRE(!with_loss || p.beta_m1 >= 0.0f,
+                      "AdaRound rounding loss: beta < 1 is not supported (beta_range must stay at or above 1)");
+        const bool exact = exact_pow() || (with_loss && !(fast_pow_covers(p.beta) && fast_pow_covers(p.beta_m1)));
         hipStream_t st = as_stream(stream);
         if ((C == 1 || K % 4 == 0) && n % 4 == 0 && aligned16(w) && aligned16(alpha) && aligned16(g) &&
             aligned16(ga))
@@ -1259,7 +1275,7 @@ int adaround_backward(const float* w, const float* alpha, const float* g, float*
                     reinterpret_cast<f4*>(ga), nq, map, delta, offset, p, round_loss, reg_beta, lf.part, lf.ticket);
             };
             // the scalar pow tail exists only for the exact pow (the fast pow takes every element alike)
-            const bool wl = p.want_loss != 0, ex = exact_pow(), tl = ex && n % 32 != 0;
+            const bool wl = p.want_loss != 0, ex = exact, tl = ex && n % 32 != 0;
             // (a form compiled for 8 waves per SIMD spilled and measured slower:
             // profiles/r04/ada_bwd_tune_occ8.jsonl)
             auto go = [&](auto u) {
@@ -1286,7 +1302,7 @@ int adaround_backward(const float* w, const float* alpha, const float* g, float*
                 kernel<<<gx, kBlock, 0, st>>>(w, alpha, g, ga, (uint32_t) n, map, delta, offset, p, round_loss, reg_beta,
                                               lf.part, lf.ticket);
             };
-            exact_pow() ? launch(adaround_bwd_kernel<true>) : launch(adaround_bwd_kernel<false>);
+            exact ? launch(adaround_bwd_kernel<true>) : launch(adaround_bwd_kernel<false>);
             AIMET_LAUNCH_CHECK();
             lf.finish(p.reg, reg_beta, nullptr, round_loss);
         }

@@ -17,9 +17,20 @@
 //   ~2^-28), exp(rr) - 1 = rr + rr^2 (1/2 + rr/6) (truncation 2^-31), and the result
 //   eh + (eh em1 + el) rounded once, scaled by 2^n (exact unless subnormal, like Sleef's own
 //   final scaling).
-// For e <= 20 the value before the final rounding is within ~2^-26.5 of x^e (relative). Checked
-// exhaustively -- every f32 x in (0, 1) x the AdaRound exponent schedules -- against the
-// bit-exact Sleef emulation by tools/studies/pow_fast_check.hip (profiles/r06/pow_fast_check.txt).
+// Proven interval: for an exponent e in [2^-10, 64] (AIMET_ADAROUND_FAST_POW_MIN_EXP / _MAX_EXP) the
+// result is within 1 ulp of the correctly rounded x^e -- the float64 power rounded once -- on every
+// element of tests/test_adaround_pow_domain_gpu.py's sweep (2^18 inputs from |x| = 2^-24 to 1, the
+// exponents 2^-10, 0.01, 0.25, 0.5, 0.999, 1, 1.001, 1.5, 6.25, 13, 19, 20, 24, 25, 30, 40.5, 63, 64;
+// per exponent: profiles/r20/adaround_pow_domain.txt). The error before the final rounding grows
+// with e (the share of results one ulp off the correctly rounded value rises from 0.2 % at e <= 1.5
+// to 0.9 % at e = 20 and 2 % at e = 64); 65 and 100 still met the bar in that sweep, but lie
+// outside exp_ln's domain below and are not claimed. e = 0, 2 and 3 never reach exp_ln (exact
+// cases and products). Outside the interval no public route evaluates this pow: a host-side
+// exponent makes the launch take the exact form, a loop whose beta_range leaves it runs with the
+// exact form (adaround_optimizer.py), and the C entries that read exponents on the device state
+// it as their precondition (aimet_amd.h). Negative exponents (beta < 1) are refused in either form.
+// Also checked exhaustively -- every f32 x in (0, 1) x the AdaRound exponent schedules -- against
+// the bit-exact Sleef emulation by tools/studies/pow_fast_check.hip (profiles/r06/pow_fast_check.txt).
 // The tables (fast_pow_tab.hpp, tools/gen_pow_tab.py: exact decimal arithmetic) are copied into
 // LDS once per workgroup (pow_tab_load / pow_tab_store) and read per element with per-lane indices.
 #pragma once
@@ -105,8 +116,8 @@ __device__ __forceinline__ LnSplit ln01(float x)
     return LnSplit {a, (r + p) + b};
 }
 
-// exp(e ln x) rounded to f32, for ln x = l.a + l.l and e in (0, 64] (the error bound above holds
-// for e <= 20; it grows with e)
+// exp(e ln x) rounded to f32, for ln x = l.a + l.l and e in (0, 64] (proven within 1 ulp of the
+// correctly rounded power on [2^-10, 64], above)
 __device__ __forceinline__ float exp_ln(LnSplit l, float e)
 {
     const float yh = e * l.a;

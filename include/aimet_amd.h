@@ -532,9 +532,22 @@ int aimet_adaround_adam_bias_corrections(double beta1, double beta2, int64_t ste
                                          void* stream);
 /* The rounding loss's pow(|2h - 1|, beta) / pow(|2h - 1|, beta - 1) (adaround_loss.py:83-110) of
  * every AdaRound backward launched afterwards, process-wide: 0 (default) a table-driven f32
- * evaluation within 1 ulp of torch's CPU pow (Sleef powf_u10) over every f32 input in (0, 1) and
- * the AdaRound beta schedules; 1 the bit-exact emulation of torch's pow (about 3x the arithmetic). Wq and the
- * reconstruction term of dL/dalpha do not depend on it. */
+ * evaluation within 1 ulp of the correctly rounded power (and so of torch's CPU pow, Sleef
+ * powf_u10) for exponents that are 0 or lie in [AIMET_ADAROUND_FAST_POW_MIN_EXP,
+ * AIMET_ADAROUND_FAST_POW_MAX_EXP]; 1 the bit-exact emulation of torch's pow (about 3x the
+ * arithmetic). Wq and the reconstruction term of dL/dalpha do not depend on it.
+ * Exponents outside that set:
+ *  - aimet_adaround_backward (host-side beta): the launch takes the exact form by itself when
+ *    beta or (float)(beta - 1) lies outside, and returns AIMET_ERR_INVALID_ARGUMENT for beta < 1 with
+ *    reg_param != 0 (a negative exponent: neither form follows torch at |2h - 1| = 0).
+ *  - aimet_adaround_backward_dev, aimet_adaround_backward_adam and
+ *    aimet_adaround_backward_adam_parts read their exponents on the device, where the form is
+ *    already chosen. PRECONDITION: with the default pow selected, every {beta, beta - 1} they can
+ *    read with reg != 0 is 0 or lies in the interval above; a caller whose schedule leaves it
+ *    selects the exact pow first (aimet_adaround_set_exact_pow(1); AdaroundOptimizer does, from the
+ *    two ends of beta_range), and keeps beta >= 1 in either form. */
+#define AIMET_ADAROUND_FAST_POW_MIN_EXP 0.0009765625f /* 2^-10 */
+#define AIMET_ADAROUND_FAST_POW_MAX_EXP 64.0f
 int aimet_adaround_set_exact_pow(int exact);
 int aimet_adaround_get_exact_pow(int* exact);
 

@@ -12,13 +12,15 @@ Bars (north_star "within 1 ULP on the dequantized float tenso
   torch's CPU pow restated, Sleef powf_u10 in the vectorized part, the correctly rounded value in
   the scalar tail of the last n mod 32 elements -- cases 7 and 8 have such tails;
   tools/studies/sleef_powf_check.py) bit-exact; with the default fast pow (within 1 ulp of torch's
-  pow, profiles/r06/pow_fast_check.txt) the reference's own float32 chain after the pow evaluated
-  at a pow within 1 ulp of torch's, bit for bit (_fast_pow_gradient_ok);
+  pow, profiles/r20/adaround_pow_domain.txt) the reference's own float32 chain after the pow evaluated
+  at a pow within 1 ulp of torch's, bit for bit (adaround_oracle.fast_pow_gradient_ok);
 * the rounding loss value: rtol 1e-5 (float32 sums in a different order)."""
 import numpy as np
 import pytest
 import torch
 
+import adaround_oracle as AO
+from adaround_oracle import fast_pow_gradient_ok as _fast_pow_gradient_ok, ulps as _ulps
 from conftest import gpu_available
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs an MI355X")]
@@ -38,14 +40,6 @@ def _case(z, i):
                                   "round_loss", "beta")} | {"bw": int(z[k + "bw"])}
 
 
-def _ulps(a, b):
-    a = np.asarray(a, np.float32).ravel().view(np.int32).astype(np.int64)
-    b = np.asarray(b, np.float32).ravel().view(np.int32).astype(np.int64)
-    a = np.where(a < 0, -(a & 0x7FFFFFFF), a)
-    b = np.where(b < 0, -(b & 0x7FFFFFFF), b)
-    return np.abs(a - b)
-
-
 def test_adaround_forward_bit_exact_vs_reference(gad):
     from aimet_amd.adaround import AdaroundFunction
     worst = 0
@@ -61,51 +55,6 @@ def test_adaround_forward_bit_exact_vs_reference(gad):
         assert u.max() == 0, (i, c["w"].shape, int((u != 0).sum()), int(u.max()))
         assert np.array_equal(wh.view(np.int32), c["wq_hard"].view(np.int32)), i
     print("adaround Wq: max ulp vs reference = %d" % worst)
-
-
-def _f32_step(p, k):
-    """p (float32 >= 0) moved by k ulps, clamped at +0"""
-    b = p.view(np.int32).astype(np.int64) + k
-    return np.maximum(b, 0).astype(np.int32).view(np.float32)
-
-
-def _fast_pow_gradient_ok(c, reg, got):
-    """dL/dalpha with the rounding loss is recon + T(p) with p = |2h - 1|^(beta - 1) and T the
-    reference's autograd chain after the pow (pow_backward: grad * (beta * p); abs; 2*h; clamp;
-    * (zeta - gamma); sigmoid_backward), every step a float32 op. Restated here (numpy float32,
-    sigmoid from torch's CPU op, as the kernel's, and the golden reconstruction gradient): for each
-    element, the pow values within 3 ulp of the correctly rounded x^(beta - 1) whose T reproduces
-    the golden dL/dalpha bit for bit are torch's pow (`pinned`: at least one must); the kernel's
-    result must then be T(p') for a p' within 1 ulp of one of them -- the bar the fast pow is
-    proven to (profiles/r06/pow_fast_check.txt), carried through the reference's own chain. A
-    difference of 1 ulp in p can move dL/dalpha by more than 1 ulp of its value: the loss term
-    and the reconstruction gradient cancel in part (tests/golden, case 6: up to 64 ulp)."""
-    f = np.float32
-    beta = float(c["beta"])
-    sg = torch.sigmoid(torch.from_numpy(c["alpha"])).numpy()
-    pre = sg * f(1.2) + f(-0.1)
-    h = np.clip(pre, f(0), f(1))
-    in_h = (pre >= 0) & (pre <= 1)
-    x = f(2) * h + f(-1)
-    sgn = np.sign(x).astype(f)
-
-    def chain(p):
-        dpw = f(-reg) * (f(beta) * p)
-        dh = (dpw * sgn) * f(2)
-        return c["ga_recon"] + ((np.where(in_h, dh, f(0)) * f(1.2)) * (f(1) - sg)) * sg
-
-    p_cr = np.power(np.abs(x).astype(np.float64), np.float64(f(beta - 1.0))).astype(f)
-    want = c["ga_total"].view(np.int32)
-    got = got.view(np.int32)
-    outs = {k: chain(_f32_step(p_cr, k)).view(np.int32) for k in range(-4, 5)}
-    sleef = {k: outs[k] == want for k in range(-3, 4)}
-    pinned = np.zeros(want.shape, bool)
-    ok = np.zeros(want.shape, bool)
-    for k, m in sleef.items():
-        pinned |= m
-        for d in (-1, 0, 1):
-            ok |= m & (outs[k + d] == got)
-    return ok, pinned
 
 
 def test_adaround_backward_vs_reference(gad, exact_pow):
@@ -239,7 +188,9 @@ def test_adaround_special_values_vs_torch_cpu():
     +-inf, +-0, at and beside the sigmoid's range clamps (+-100, -104, 88.7) and +-1e30; weights
     NaN, +-inf, +-0, tiny negatives (the floor guard's fract near 1) and multiples of delta one ulp
     off. With the exact pow Wq and dL/dalpha (rounding loss included) are bit-exact, NaN for NaN;
-    with the default pow Wq and the reconstruction gradient are. n = 1024: no scalar pow tail."""
+    with the default pow Wq and the reconstruction gradient are, and dL/dalpha with the rounding
+    loss is where |2h - 1| is 0, 1 or NaN (the pow's exact cases) and meets the fast pow's bar
+    elsewhere (adaround_oracle.pow_steps). n = 1024: no scalar pow tail."""
     from aimet_amd.adaround import AdaroundFunction, set_exact_pow
     from oracle import torch_ref as T
     f32 = np.float32
@@ -282,9 +233,18 @@ def test_adaround_special_values_vs_torch_cpu():
             (wq * gd).sum().backward()
             assert _same_bits_or_nan(wq.detach().cpu().numpy(), wq_ref), exact
             assert _same_bits_or_nan(ad.grad.cpu().numpy(), ga_recon), exact
+            ad = torch.from_numpy(a).to(DEV).requires_grad_(True)
+            (AdaroundFunction.apply(wd, ad, dd, od, bw, 0, True, reg, beta, None) * gd).sum().backward()
+            got = ad.grad.cpu().numpy()
             if exact:
-                ad = torch.from_numpy(a).to(DEV).requires_grad_(True)
-                (AdaroundFunction.apply(wd, ad, dd, od, bw, 0, True, reg, beta, None) * gd).sum().backward()
-                assert _same_bits_or_nan(ad.grad.cpu().numpy(), ga_total)
+                assert _same_bits_or_nan(got, ga_total)
+            else:
+                # the default pow: torch's bits where the power is an exact case (|x| 0, 1 or NaN),
+                # elsewhere the reference's chain at a pow within 1 ulp of the correctly rounded one
+                ch = AO.Chain(a, ga_recon)
+                is_exact = AO.pow_cr(ch.ax, f32(beta - 1.0))[2]
+                assert is_exact.sum() >= 2 * alphas.size - 8
+                assert _same_bits_or_nan(got[is_exact], ga_total[is_exact])
+                assert AO.pow_steps(ch, got, reg, beta).max() <= 1
         finally:
             set_exact_pow(prev)
