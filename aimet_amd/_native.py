@@ -119,6 +119,8 @@ _PROTOTYPES = {
     "aimet_version": [],
     "aimet_device_count": [],
     "aimet_capture_pool_limit": [_i64, ctypes.POINTER(_i64)],
+    "aimet_scratch_live": [_i64p, _i64p],
+    "aimet_scratch_taken": [_i64p],
     "aimet_get_computed_encodings": [_i32, ctypes.c_double, ctypes.c_double, _int, _int, _int, _enc_p],
     "aimet_fill_encoding_info": [_i32, ctypes.c_double, ctypes.c_double, _enc_p],
     "aimet_compute_partial_encoding": [_i32, _enc_p, _int, _int, _int],

@@ -718,9 +718,9 @@ struct LossFold
     float* part      = nullptr;
     unsigned* ticket = nullptr;
     FoldBuffers fb;
+    Scratch<float> fallback;
     hipStream_t s;
     unsigned grid = 0;
-    bool scratch  = false;
     LossFold(const float* round_loss, unsigned g, hipStream_t st) : s(st), grid(g)
     {
         if (!round_loss)
@@ -730,32 +730,18 @@ struct LossFold
         part   = fb.part;
         if (!ticket)
         {
-            part    = static_cast<float*>(scratch_alloc(sizeof(float) * grid, st));
-            scratch = true;
+            fallback = Scratch<float>(grid, st);
+            part     = fallback.get();
         }
     }
     // after the backward's launch: the fold of its partials when they had no ticket
     void finish(float reg, const float* reg_beta, const int64_t* it_next, float* round_loss)
     {
-        if (!scratch)
+        if (!fallback)
             return;
         round_loss_fold_kernel<<<1, kBlock, 0, s>>>(part, grid, reg, reg_beta, it_next, round_loss);
         AIMET_LAUNCH_CHECK();
     }
-    ~LossFold()
-    {
-        try
-        {
-            if (scratch)
-                scratch_free(part, s);
-            fold_buffers_release(fb, s);
-        }
-        catch (...)   // a failing event record: the block is leaked, never handed out again
-        {
-        }
-    }
-    LossFold(const LossFold&)            = delete;
-    LossFold& operator=(const LossFold&) = delete;
 };
 
 bool aligned16(const void* p)

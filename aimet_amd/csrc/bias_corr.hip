@@ -130,14 +130,9 @@ int aimet_bc_channel_sums(const float* x, int64_t outer, int64_t C, int64_t inne
         require_channel_alignment("channel sums", {x}, {acc_dev});
         hipStream_t s             = as_stream(stream);
         const auto [part, nsplit] = launch_channel_reduce<ChannelSum>(x, outer, C, inner, s);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess)
-        {
-            fold(part, nsplit, C, acc_dev, s);
-            e = hipGetLastError();
-        }
-        scratch_free(part, s);
-        AIMET_HIP_CHECK(e);
+        AIMET_LAUNCH_CHECK();
+        fold(part.get(), nsplit, C, acc_dev, s);
+        AIMET_LAUNCH_CHECK();
         g_launches.add(2);
     });
 }
@@ -197,11 +192,9 @@ int aimet_bc_analytical(const aimet_bc_analytical_job* jobs, int64_t count, void
             max_cout          = std::max(max_cout, w.cout);
         }
         hipStream_t s = as_stream(stream);
-        auto* dev     = static_cast<AnaJob*>(upload_async(table.data(), table.size() * sizeof(AnaJob), s));
-        bc_analytical_kernel<<<dim3((unsigned) max_cout, (unsigned) count), kBcBlock, 0, s>>>(dev);
-        hipError_t e = hipGetLastError();
-        scratch_free(dev, s);
-        AIMET_HIP_CHECK(e);
+        auto dev      = Scratch<AnaJob>::upload(table, s);
+        bc_analytical_kernel<<<dim3((unsigned) max_cout, (unsigned) count), kBcBlock, 0, s>>>(dev.get());
+        AIMET_LAUNCH_CHECK();
         g_launches.add(1);
     });
 }

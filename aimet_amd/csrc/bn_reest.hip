@@ -226,34 +226,25 @@ int aimet_bnre_forward(const float* x, int64_t outer, int64_t C, int64_t inner, 
             return;
         }
         const auto [part, nsplit] = launch_channel_reduce<Moments>(x, outer, C, inner, s);
-        auto* ab     = static_cast<float2*>(scratch_alloc((size_t) C * sizeof(float2), s));
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess)
+        Scratch<float2> ab((size_t) C, s);
+        AIMET_LAUNCH_CHECK();
+        bnre_fold_kernel<<<(unsigned) ceil_div(C, kBlk), kBlk, 0, s>>>(part.get(), nsplit, C, x, inner, (double) n,
+                                                                      gamma, beta, (double) eps, sum_mean_dev,
+                                                                      sum_var_dev, ab.get());
+        AIMET_LAUNCH_CHECK();
+        const int64_t total = n * C;
+        if (((xa ^ ya) & 15) == 0)
         {
-            bnre_fold_kernel<<<(unsigned) ceil_div(C, kBlk), kBlk, 0, s>>>(part, nsplit, C, x, inner, (double) n, gamma,
-                                                                          beta, (double) eps, sum_mean_dev,
-                                                                          sum_var_dev, ab);
-            e = hipGetLastError();
+            const int64_t head   = std::min<int64_t>((int64_t) (((16 - (xa & 15)) & 15) >> 2), total);
+            const int64_t blocks = clamp64(ceil_div((total - head) / 4, kBlk), 1, kMaxNormBlocks);
+            bnre_normalise_kernel<true><<<(unsigned) blocks, kBlk, 0, s>>>(x, y, total, C, inner, head, ab.get());
         }
-        if (e == hipSuccess)
+        else
         {
-            const int64_t total = n * C;
-            if (((xa ^ ya) & 15) == 0)
-            {
-                const int64_t head   = std::min<int64_t>((int64_t) (((16 - (xa & 15)) & 15) >> 2), total);
-                const int64_t blocks = clamp64(ceil_div((total - head) / 4, kBlk), 1, kMaxNormBlocks);
-                bnre_normalise_kernel<true><<<(unsigned) blocks, kBlk, 0, s>>>(x, y, total, C, inner, head, ab);
-            }
-            else
-            {
-                const int64_t blocks = clamp64(ceil_div(total, kBlk), 1, kMaxNormBlocks);
-                bnre_normalise_kernel<false><<<(unsigned) blocks, kBlk, 0, s>>>(x, y, total, C, inner, 0, ab);
-            }
-            e = hipGetLastError();
+            const int64_t blocks = clamp64(ceil_div(total, kBlk), 1, kMaxNormBlocks);
+            bnre_normalise_kernel<false><<<(unsigned) blocks, kBlk, 0, s>>>(x, y, total, C, inner, 0, ab.get());
         }
-        scratch_free(part, s);
-        scratch_free(ab, s);
-        AIMET_HIP_CHECK(e);
+        AIMET_LAUNCH_CHECK();
         g_launches.add(3);
     });
 }
@@ -280,11 +271,9 @@ int aimet_bnre_finish(const aimet_bnre_finish_job* jobs, int64_t count, void* st
             max_c             = std::max(max_c, j.C);
         }
         hipStream_t s = as_stream(stream);
-        auto* dev     = static_cast<FinishJob*>(upload_async(table.data(), table.size() * sizeof(FinishJob), s));
-        bnre_finish_kernel<<<dim3((unsigned) ceil_div(max_c, kBlk), (unsigned) count), kBlk, 0, s>>>(dev);
-        hipError_t e = hipGetLastError();
-        scratch_free(dev, s);
-        AIMET_HIP_CHECK(e);
+        auto dev      = Scratch<FinishJob>::upload(table, s);
+        bnre_finish_kernel<<<dim3((unsigned) ceil_div(max_c, kBlk), (unsigned) count), kBlk, 0, s>>>(dev.get());
+        AIMET_LAUNCH_CHECK();
         g_launches.add(1);
     });
 }

@@ -106,6 +106,19 @@ int aimet_capture_pool_limit(int64_t arena_floats, int64_t* previous)
     });
 }
 
+int aimet_scratch_live(int64_t* blocks, int64_t* bytes)
+{
+    return guarded([&] { scratch_live(blocks, bytes); });
+}
+
+int aimet_scratch_taken(int64_t* blocks)
+{
+    return guarded([&] {
+        AIMET_REQUIRE(blocks != nullptr, "output is null");
+        *blocks = scratch_taken();
+    });
+}
+
 int aimet_get_computed_encodings(int32_t bw, double mn, double mx, int sym, int strict, int unsign,
                                  aimet_tf_encoding* out)
 {

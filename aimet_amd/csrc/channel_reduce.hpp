@@ -360,7 +360,7 @@ inline ChannelPlan plan_channel_reduce(bool base16, int64_t outer, int64_t C, in
 
 struct ChannelPartials
 {
-    double* part;   // Acc::N * nsplit * C doubles of scratch_alloc: the caller folds and frees them
+    Scratch<double> part;   // Acc::N * nsplit * C doubles, released on s when the caller has folded them
     int64_t nsplit;
 };
 
@@ -369,7 +369,8 @@ template <class Acc>
 ChannelPartials launch_channel_reduce(const float* x, int64_t outer, int64_t C, int64_t inner, hipStream_t s)
 {
     const ChannelPlan p = plan_channel_reduce((reinterpret_cast<uintptr_t>(x) & 15) == 0, outer, C, inner);
-    auto* part = static_cast<double*>(scratch_alloc((size_t) (Acc::N * p.nsplit * C) * sizeof(double), s));
+    Scratch<double> owner((size_t) (Acc::N * p.nsplit * C), s);
+    double* part = owner.get();
     const dim3 grid((unsigned) p.gx, (unsigned) p.nsplit);
     switch (p.form)
     {
@@ -388,7 +389,7 @@ ChannelPartials launch_channel_reduce(const float* x, int64_t outer, int64_t C, 
                                                                      outer * inner, p.chunk, part);
         break;
     }
-    return {part, p.nsplit};
+    return {std::move(owner), p.nsplit};
 }
 
 }   // namespace aimet_amd

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "aimet_amd.h"
+#include "scratch.hpp"
 #include "vec_types.hpp"
 
 namespace aimet_amd
@@ -241,29 +242,25 @@ __device__ __forceinline__ float glibc_fmaxf(float x, float y)
     return (x > y || __builtin_isnan(y)) ? x : y;
 }
 
-// upload.cpp: stream-ordered device copy of a small host table without blocking the host
-// (pinned staging ring); release with scratch_free(ptr, s) after the consuming launches.
-void* upload_async(const void* src, size_t bytes, hipStream_t s);
-// Stream-ordered device scratch without the stream-ordered pool: released blocks are reused once
-// an event recorded after their consumers has completed (upload.cpp; the pool let a job table be
-// reused under a running kernel: tests/cpp/sanitize_host.cpp).
-void* scratch_alloc(size_t bytes, hipStream_t s);
 // `count` consecutive zeroed completion counters for last-workgroup folds, or nullptr: upload.cpp
 unsigned* ticket_alloc(hipStream_t s, unsigned count = 1);
 // tickets + a partial-sum buffer of `part_floats` for one launch's last-workgroup fold; both null
 // when there is no ticket (the caller then falls back). Inside a HIP-graph capture the buffer is a
-// permanent slot of its own (no graph memory node); release with fold_buffers_release.
+// permanent slot of its own (no graph memory node); outside one it is scratch that `own` holds
+// until the FoldBuffers goes.
 struct FoldBuffers
 {
     unsigned* ticket = nullptr;
     float* part      = nullptr;
-    bool scratch     = false;
+    Scratch<float> own;
 };
 FoldBuffers fold_buffers(hipStream_t s, unsigned tickets, size_t part_floats);
-void fold_buffers_release(const FoldBuffers& f, hipStream_t s);
 // aimet_capture_pool_limit: the capture arena's cap on the current device (returns the previous one)
 size_t capture_pool_limit(size_t arena_floats);
-void scratch_free(void* p, hipStream_t s);
+// aimet_scratch_live: the scratch blocks handed out and not yet released, and their bytes
+void scratch_live(int64_t* blocks, int64_t* bytes);
+// aimet_scratch_taken: the scratch blocks handed out since the process began
+int64_t scratch_taken();
 
 // Kernel launches of one family of entry points, as its aimet_*_launch_count reports them.
 class LaunchCounter

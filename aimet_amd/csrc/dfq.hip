@@ -407,11 +407,9 @@ int aimet_dfq_bn_fold(const aimet_dfq_bn_fold_job* jobs, int64_t count, int32_t*
             max_cout          = std::max(max_cout, j.w.cout);
         }
         hipStream_t s = as_stream(stream);
-        auto* dev     = static_cast<BnJob*>(upload_async(table.data(), table.size() * sizeof(BnJob), s));
-        dfq_bn_fold_kernel<<<dim3((unsigned) max_cout, (unsigned) count), kDfqBlock, 0, s>>>(dev, status_dev);
-        hipError_t e = hipGetLastError();
-        scratch_free(dev, s);
-        AIMET_HIP_CHECK(e);
+        auto dev      = Scratch<BnJob>::upload(table, s);
+        dfq_bn_fold_kernel<<<dim3((unsigned) max_cout, (unsigned) count), kDfqBlock, 0, s>>>(dev.get(), status_dev);
+        AIMET_LAUNCH_CHECK();
         g_launches.add(1);
     });
 }
@@ -440,11 +438,10 @@ int aimet_bnre_fold_scale(const aimet_bnre_fold_scale_job* jobs, int64_t count, 
             max_cout          = std::max(max_cout, j.fold.w.cout);
         }
         hipStream_t s = as_stream(stream);
-        auto* dev     = static_cast<BnScaleJob*>(upload_async(table.data(), table.size() * sizeof(BnScaleJob), s));
-        dfq_bn_fold_scale_kernel<<<dim3((unsigned) max_cout, (unsigned) count), kDfqBlock, 0, s>>>(dev, status_dev);
-        hipError_t e = hipGetLastError();
-        scratch_free(dev, s);
-        AIMET_HIP_CHECK(e);
+        auto dev      = Scratch<BnScaleJob>::upload(table, s);
+        dfq_bn_fold_scale_kernel<<<dim3((unsigned) max_cout, (unsigned) count), kDfqBlock, 0, s>>>(dev.get(),
+                                                                                                    status_dev);
+        AIMET_LAUNCH_CHECK();
         bnre_count_launches(1);
     });
 }

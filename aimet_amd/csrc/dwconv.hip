@@ -598,8 +598,10 @@ void dw_grad_weight(const float* x, const float* grad_y, float* grad_w, float* w
     // free of allocations, e.g. inside a HIP-graph capture
     if (workspace)
         require_device_ptr(workspace, "workspace");
-    float* partial = workspace ? workspace
-                               : static_cast<float*>(scratch_alloc(sizeof(float) * (size_t) (C * S * K * K), st));
+    Scratch<float> own;
+    if (!workspace)
+        own = Scratch<float>((size_t) (C * S * K * K), st);
+    float* partial = workspace ? workspace : own.get();
     dim3 grid((unsigned) S, (unsigned) C);
     if (quads && stride == 1)
         dw_wgrad_quad_kernel<1><<<grid, kBlock, 0, st>>>(x, grad_y, partial, s, per);
@@ -613,8 +615,6 @@ void dw_grad_weight(const float* x, const float* grad_y, float* grad_w, float* w
     dw_wgrad_fold<<<(unsigned) ceil_div(C * K * K, kBlock), kBlock, 0, st>>>(partial, grad_w, (uint32_t) C,
                                                                             (uint32_t) S, (uint32_t) (K * K));
     AIMET_LAUNCH_CHECK();
-    if (!workspace)
-        scratch_free(partial, st);
 }
 
 void dw_step(const float* x_cache, const float* t_cache, const int64_t* idx_all, const int64_t* it_cur,
@@ -643,8 +643,10 @@ void dw_step(const float* x_cache, const float* t_cache, const int64_t* idx_all,
     const int64_t S  = wgrad_slices(N, C, OH, OW, &per, quads);
     if (workspace)
         require_device_ptr(workspace, "workspace");
-    float* partial = workspace ? workspace
-                               : static_cast<float*>(scratch_alloc(sizeof(float) * (size_t) (C * S * K * K), st));
+    Scratch<float> own;
+    if (!workspace)
+        own = Scratch<float>((size_t) (C * S * K * K), st);
+    float* partial = workspace ? workspace : own.get();
     // aimet_adaround_recon_grad_indexed's scale: 2 / (number of dim-1 norms)
     DwStep a {x_cache, t_cache, idx_all, it_cur, it_next, w, bias, (float) (2.0 / (double) (N * OH * OW)), act};
     dim3 grid((unsigned) S, (unsigned) C);
@@ -665,8 +667,6 @@ void dw_step(const float* x_cache, const float* t_cache, const int64_t* idx_all,
                                                                                 (uint32_t) S, (uint32_t) (K * K));
         AIMET_LAUNCH_CHECK();
     }
-    if (!workspace)
-        scratch_free(partial, st);
 }
 
 }   // namespace

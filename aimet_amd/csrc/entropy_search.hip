@@ -765,34 +765,30 @@ void launch_entropy_search_many(const TqDevice* const* ds, const int64_t* Cs, in
     for (int i = 0; i < n; ++i)
         total += Cs[i];
     // every quantizer's encodings side by side, for one copy into the caller's pinned block
-    auto* flat = pinned_dst ? static_cast<EntropyOut*>(scratch_alloc(sizeof(EntropyOut) * total, s)) : nullptr;
+    Scratch<EntropyOut> flat;
+    if (pinned_dst)
+        flat = Scratch<EntropyOut>((size_t) total, s);
     total = 0;
     for (int i = 0; i < n; ++i)
     {
-        jobs[(size_t) i] = EntJob {ds[i]->acc, ds[i]->pdf_init, ds[i]->pdf, entropy_ranges(*ds[i]), total, flat};
+        jobs[(size_t) i] = EntJob {ds[i]->acc, ds[i]->pdf_init, ds[i]->pdf, entropy_ranges(*ds[i]), total, flat.get()};
         total += Cs[i];
     }
-    auto* dj       = static_cast<EntJob*>(upload_async(jobs.data(), sizeof(EntJob) * (size_t) n, s));
+    auto dj        = Scratch<EntJob>::upload(jobs, s);
     const int grid = (int) (total < 65536 ? total : 65536);
     // asymmetric, not strict: every channel's window list first, 64 channels per wave
-    short* walks = nullptr;
+    Scratch<short> walks;
     if (!sym && !strict)
     {
-        walks = static_cast<short*>(scratch_alloc(sizeof(short) * 2 * entropy::kWindows * (size_t) total, s));
-        entropy_walk_kernel<<<(int) ((total + 63) / 64), 64, 0, s>>>(dj, n, total, walks);
+        walks = Scratch<short>(2 * entropy::kWindows * (size_t) total, s);
+        entropy_walk_kernel<<<(int) ((total + 63) / 64), 64, 0, s>>>(dj.get(), n, total, walks.get());
         AIMET_LAUNCH_CHECK();
     }
-    entropy_search_kernel<<<grid, kEntBlock, 0, s>>>(dj, n, total, sym ? 1 : 0, strict ? 1 : 0, unsign ? 1 : 0,
-                                                               bw, walks);
+    entropy_search_kernel<<<grid, kEntBlock, 0, s>>>(dj.get(), n, total, sym ? 1 : 0, strict ? 1 : 0, unsign ? 1 : 0,
+                                                     bw, walks.get());
     AIMET_LAUNCH_CHECK();
-    if (walks)
-        scratch_free(walks, s);
-    scratch_free(dj, s);
     if (flat)
-    {
-        AIMET_HIP_CHECK(hipMemcpyAsync(pinned_dst, flat, sizeof(EntropyOut) * total, hipMemcpyDeviceToHost, s));
-        scratch_free(flat, s);
-    }
+        AIMET_HIP_CHECK(hipMemcpyAsync(pinned_dst, flat.get(), sizeof(EntropyOut) * total, hipMemcpyDeviceToHost, s));
 }
 
 }   // namespace aimet_amd

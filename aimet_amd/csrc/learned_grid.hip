@@ -1219,17 +1219,16 @@ void backward_tiles(const float* x, const void* grad, float* grad_x, float* sums
     const int64_t K4 = K / 4;
     const int U      = K4 % (kBlock * 4) == 0 ? 4 : K4 % (kBlock * 2) == 0 ? 2 : 1;
     const int64_t wg = outer * C * K4 / (kBlock * U);
-    float* partial   = static_cast<float*>(scratch_alloc(sizeof(float) * 3 * wg, b.s));
+    Scratch<float> partial((size_t) (3 * wg), b.s);
     with_quads(U, [&](auto u) {
         lg_bwd_tile_kernel<decltype(u)::value, GIO><<<(unsigned) wg, kBlock, 0, b.s>>>(
             reinterpret_cast<const f4*>(x), grad, reinterpret_cast<f4*>(grad_x), FastDiv((uint32_t) K4),
-            FastDiv((uint32_t) C), (uint32_t) C, delta, offset, steps, b.mode, partial);
+            FastDiv((uint32_t) C), (uint32_t) C, delta, offset, steps, b.mode, partial.get());
     });
     AIMET_LAUNCH_CHECK();
     lg_bwd_tile_fold<<<(unsigned) ceil_div(C, kBlock), kBlock, 0, b.s>>>(
-        partial, sums, (uint32_t) outer, (uint32_t) C, (uint32_t) (K4 / (kBlock * U)), b.range);
+        partial.get(), sums, (uint32_t) outer, (uint32_t) C, (uint32_t) (K4 / (kBlock * U)), b.range);
     AIMET_LAUNCH_CHECK();
-    scratch_free(partial, b.s);
 }
 
 // per-tensor: lg_bwd_launch's tiles, one partial triple per tile, folded by lg_bwd_fold_one. IO:
@@ -1242,7 +1241,7 @@ void backward_tensor(const void* x, const void* grad, void* grad_x, float* sums,
     typedef typename LgIo<IO>::elem_t T;
     const int vec       = aligned16(x, grad, grad_x) ? 1 : 0;
     const LgBwdLaunch L = lg_bwd_launch(n);
-    float* partial      = static_cast<float*>(scratch_alloc(sizeof(float) * 3 * L.ntiles, b.s));
+    Scratch<float> partial((size_t) 3 * L.ntiles, b.s);
     auto xs = static_cast<const T*>(x);
     auto gs = static_cast<const T*>(grad);
     auto os = static_cast<T*>(grad_x);
@@ -1250,15 +1249,14 @@ void backward_tensor(const void* x, const void* grad, void* grad_x, float* sums,
         constexpr int MD = decltype(md)::value;
         if constexpr (IO == IO_F32)
             lg_bwd_tensor_kernel<kLgTileSteps, MD><<<L.grid, kBlock, 0, b.s>>>(xs, gs, os, n, delta, offset, steps,
-                                                                               partial, vec, L.ntiles);
+                                                                               partial.get(), vec, L.ntiles);
         else
             lg_bwd16_tensor_kernel<IO, kLgTileSteps, MD><<<L.grid16, kBlock, 0, b.s>>>(
-                xs, gs, os, n, delta, offset, steps, partial, vec, L.ntiles);
+                xs, gs, os, n, delta, offset, steps, partial.get(), vec, L.ntiles);
     });
     AIMET_LAUNCH_CHECK();
-    lg_bwd_fold_one<<<1, kBlock, 0, b.s>>>(partial, L.ntiles, sums, b.range);
+    lg_bwd_fold_one<<<1, kBlock, 0, b.s>>>(partial.get(), L.ntiles, sums, b.range);
     AIMET_LAUNCH_CHECK();
-    scratch_free(partial, b.s);
 }
 
 }   // namespace
@@ -1451,8 +1449,10 @@ int aimet_lg_backward(const float* x, const float* grad, float* grad_x, float* s
             if (splits > per)
                 splits = per > 0 ? per : 1;
             dim3 grid((unsigned) (C < 65536 ? C : 65536), (unsigned) splits);
-            float* partial = splits > 1 ? static_cast<float*>(scratch_alloc(sizeof(float) * 3 * C * splits, b.s))
-                                        : sums;
+            Scratch<float> own;
+            if (splits > 1)
+                own = Scratch<float>((size_t) (3 * C * splits), b.s);
+            float* partial = splits > 1 ? own.get() : sums;
             lg_bwd_channel_vec_kernel<<<grid, kBlock, 0, b.s>>>(
                 reinterpret_cast<const f4*>(x), reinterpret_cast<const f4*>(grad), reinterpret_cast<f4*>(grad_x),
                 outer, C, K4, FastDiv((uint32_t) (K4 > 0 ? K4 : 1)), delta, offset, num_steps, b.mode, partial);
@@ -1462,7 +1462,6 @@ int aimet_lg_backward(const float* x, const float* grad, float* grad_x, float* s
                 lg_bwd_tile_fold<<<(unsigned) ceil_div(C, kBlock), kBlock, 0, b.s>>>(partial, sums, 1u, (uint32_t) C,
                                                                                    (uint32_t) splits, b.range);
                 AIMET_LAUNCH_CHECK();
-                scratch_free(partial, b.s);
                 return;
             }
         }

@@ -525,29 +525,27 @@ void launch_mse_search_many(const TqDevice* const* ds, const int64_t* Cs, int n,
     for (int i = 0; i < n; ++i)
         chans += Cs[i];
     // the encodings of every quantizer side by side, for one copy into the caller's pinned block
-    auto* flat = pinned_dst ? static_cast<aimet_tf_encoding*>(scratch_alloc(sizeof(aimet_tf_encoding) * chans, s))
-                            : nullptr;
+    Scratch<aimet_tf_encoding> flat;
+    if (pinned_dst)
+        flat = Scratch<aimet_tf_encoding>((size_t) chans, s);
     chans = 0;
     for (int i = 0; i < n; ++i)
     {
         const int splits = mse_splits(Cs[i]);
-        jobs[(size_t) i] = MseJob {*ds[i], Cs[i], splits, work, chans, flat};
+        jobs[(size_t) i] = MseJob {*ds[i], Cs[i], splits, work, chans, flat.get()};
         work += Cs[i] * splits;
         chans += Cs[i];
     }
-    auto* dj = static_cast<MseJob*>(upload_async(jobs.data(), sizeof(MseJob) * (size_t) n, s));
+    auto dj = Scratch<MseJob>::upload(jobs, s);
     mse_search_many_kernel<<<(unsigned) (work < 65536 ? work : 65536), kBlock, 0, s>>>(
-        dj, n, work, bw, sym ? 1 : 0, strict ? 1 : 0, unsign ? 1 : 0);
+        dj.get(), n, work, bw, sym ? 1 : 0, strict ? 1 : 0, unsign ? 1 : 0);
     AIMET_LAUNCH_CHECK();
-    mse_finish_many_kernel<<<(unsigned) ceil_div(chans, kBlock), kBlock, 0, s>>>(dj, n, chans, bw, sym ? 1 : 0,
+    mse_finish_many_kernel<<<(unsigned) ceil_div(chans, kBlock), kBlock, 0, s>>>(dj.get(), n, chans, bw, sym ? 1 : 0,
                                                                                  strict ? 1 : 0, unsign ? 1 : 0);
     AIMET_LAUNCH_CHECK();
-    scratch_free(dj, s);
     if (flat)
-    {
-        AIMET_HIP_CHECK(hipMemcpyAsync(pinned_dst, flat, sizeof(aimet_tf_encoding) * chans, hipMemcpyDeviceToHost, s));
-        scratch_free(flat, s);
-    }
+        AIMET_HIP_CHECK(
+            hipMemcpyAsync(pinned_dst, flat.get(), sizeof(aimet_tf_encoding) * chans, hipMemcpyDeviceToHost, s));
 }
 
 void launch_mse_search(const TqDevice& d, int64_t C, int bw, bool sym, bool strict, bool unsign, hipStream_t s)

@@ -570,7 +570,10 @@ int aimet_adaround_pw_step(const float* x_cache, const float* target_cache, cons
         if (workspace)
             require_device_ptr(workspace, "workspace");
         const size_t ws_elems = ((size_t) grid + kPwSlices) * (size_t) pairs;
-        float* part = workspace ? workspace : static_cast<float*>(scratch_alloc(sizeof(float) * ws_elems, st));
+        Scratch<float> own;
+        if (!workspace)
+            own = Scratch<float>(ws_elems, st);
+        float* part  = workspace ? workspace : own.get();
         float* part2 = part + (size_t) grid * pairs;
         PwStep a {x_cache, target_cache, idx_all, it_cur, it_next, w, bias,
                   (float) (2.0 / (double) (N * HW)), act, (uint32_t) N, (uint32_t) Cin, (uint32_t) Cout,
@@ -607,8 +610,6 @@ int aimet_adaround_pw_step(const float* x_cache, const float* target_cache, cons
             pw_fold_final<<<gx, kBlock, 0, st>>>(part2, grad_w, (uint32_t) pairs, nslices);
             AIMET_LAUNCH_CHECK();
         }
-        if (!workspace)
-            scratch_free(part, st);
     });
 }
 

@@ -121,7 +121,7 @@ void block_layout_strides(const aimet_broadcast_shape_info& si, std::vector<int6
 }
 
 // [4][E] float table {min, max, delta, offset} of the host encodings, uploaded stream-ordered
-float* encoding_table(const aimet_tf_encoding* encs, int64_t E, hipStream_t s)
+Scratch<float> encoding_table(const aimet_tf_encoding* encs, int64_t E, hipStream_t s)
 {
     std::vector<float> t(4 * (size_t) E);
     for (int64_t i = 0; i < E; ++i)
@@ -131,7 +131,7 @@ float* encoding_table(const aimet_tf_encoding* encs, int64_t E, hipStream_t s)
         t[2 * E + i] = (float) encs[i].delta;
         t[3 * E + i] = (float) encs[i].offset;
     }
-    return static_cast<float*>(upload_async(t.data(), t.size() * sizeof(float), s));
+    return Scratch<float>::upload(t, s);
 }
 
 void copy_through(const float* in, float* out, int64_t n, hipStream_t s)
@@ -248,10 +248,8 @@ void per_channel(aimet_qc_quantize_info* info, int mode, const float* in, float*
             K *= shape[i];
     }
     auto qdq = [&] {
-        float* t = encoding_table(info->encodings, C, s);
-        int rc   = aimet_qdq_per_channel(in, out, outer, C, K, t, info->rounding_mode, next_seed(), stream);
-        scratch_free(t, s);
-        check(rc);
+        const Scratch<float> t = encoding_table(info->encodings, C, s);
+        check(aimet_qdq_per_channel(in, out, outer, C, K, t.get(), info->rounding_mode, next_seed(), stream));
     };
     switch (mode)
     {
@@ -293,24 +291,20 @@ void broadcast(aimet_qc_quantize_info* info, int mode, const float* in, float* o
     auto stats = [&] {
         require_quantizer(info, E);
         const float* buf = in;
-        float* tmp       = nullptr;
+        Scratch<float> tmp;
         if (!si.contiguous_blocks && n > 0)
         {
-            tmp = static_cast<float*>(scratch_alloc(sizeof(float) * n, s));
-            check(aimet_copy_to_contiguous_block_layout(in, tmp, &si, stream));
-            buf = tmp;
+            tmp = Scratch<float>((size_t) n, s);
+            check(aimet_copy_to_contiguous_block_layout(in, tmp.get(), &si, stream));
+            buf = tmp.get();
         }
-        int rc = aimet_tq_update_stats(info->quantizer, buf, 1, E, E ? n / E : 0, stream);
-        if (tmp)
-            scratch_free(tmp, s);
-        check(rc);
+        check(aimet_tq_update_stats(info->quantizer, buf, 1, E, E ? n / E : 0, stream));
     };
     auto qdq = [&] {
-        float* t = encoding_table(info->encodings, E, s);
-        int rc   = aimet_qdq_broadcast(in, out, n, si.num_dims, si.tensor_strides, si.encoding_strides, t, t + E,
-                                       t + 2 * E, t + 3 * E, stream);
-        scratch_free(t, s);
-        check(rc);
+        const Scratch<float> table = encoding_table(info->encodings, E, s);
+        const float* t             = table.get();
+        check(aimet_qdq_broadcast(in, out, n, si.num_dims, si.tensor_strides, si.encoding_strides, t, t + E, t + 2 * E,
+                                  t + 3 * E, stream));
     };
     switch (mode)
     {

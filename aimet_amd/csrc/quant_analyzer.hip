@@ -182,29 +182,24 @@ void launch_sq_err(const void* ref_v, const void* x_v, int64_t n, double scale, 
     const T* x        = static_cast<const T*>(x_v);
     const uintptr_t ra = reinterpret_cast<uintptr_t>(ref) & 15, xa = reinterpret_cast<uintptr_t>(x) & 15;
     int64_t blocks;
-    double* part;
+    Scratch<double> part;
     if (ra == xa)
     {
         const int64_t head = std::min<int64_t>((int64_t) (((16 - ra) & 15) / sizeof(T)), n);
         const int64_t nv   = (n - head) / EPV;
         blocks             = stream_blocks(nv, kQaBlock * kQaVecPerLane);
-        part               = static_cast<double*>(scratch_alloc((size_t) blocks * 2 * sizeof(double), s));
-        qa_sq_err_vec_kernel<IO><<<(unsigned) blocks, kQaBlock, 0, s>>>(ref, x, n, head, nv, part);
+        part               = Scratch<double>((size_t) blocks * 2, s);
+        qa_sq_err_vec_kernel<IO><<<(unsigned) blocks, kQaBlock, 0, s>>>(ref, x, n, head, nv, part.get());
     }
     else
     {
         blocks = stream_blocks(n, kQaBlock * kQaVecPerLane * EPV);
-        part   = static_cast<double*>(scratch_alloc((size_t) blocks * 2 * sizeof(double), s));
-        qa_sq_err_elem_kernel<IO><<<(unsigned) blocks, kQaBlock, 0, s>>>(ref, x, n, part);
+        part   = Scratch<double>((size_t) blocks * 2, s);
+        qa_sq_err_elem_kernel<IO><<<(unsigned) blocks, kQaBlock, 0, s>>>(ref, x, n, part.get());
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess)
-    {
-        qa_fold_kernel<<<1, kQaBlock, 0, s>>>(part, blocks, ceil_div(blocks, kQaBlock), scale, acc);
-        e = hipGetLastError();
-    }
-    scratch_free(part, s);
-    AIMET_HIP_CHECK(e);
+    AIMET_LAUNCH_CHECK();
+    qa_fold_kernel<<<1, kQaBlock, 0, s>>>(part.get(), blocks, ceil_div(blocks, kQaBlock), scale, acc);
+    AIMET_LAUNCH_CHECK();
     g_launches.add(2);
 }
 

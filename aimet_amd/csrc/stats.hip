@@ -1133,46 +1133,22 @@ void launch_stats_table(const StatsJob* dj, int n, uint64_t mm, uint64_t hb, boo
     }
 }
 
-// The host side of every *_many wrapper: upload the job table, run the caller's launches over the
-// device copy, release the table -- and `extra`, a scratch block those launches use (or nullptr) --
-// on s, behind the launches. Both are released when the upload or a launch check throws, too.
-template <class Job, class Launches>
-static void with_job_table(const std::vector<Job>& jobs, void* extra, hipStream_t s, Launches launches)
-{
-    Job* dj      = nullptr;
-    auto release = [&]() {
-        scratch_free(extra, s);
-        scratch_free(dj, s);
-    };
-    try
-    {
-        dj = static_cast<Job*>(upload_async(jobs.data(), sizeof(Job) * jobs.size(), s));
-        launches(dj, (int) jobs.size());
-    }
-    catch (...)
-    {
-        release();
-        throw;
-    }
-    release();
-}
-
 void launch_stats_many(std::vector<StatsJob>& jobs, int phases, hipStream_t s, const std::function<void()>& between)
 {
     if (jobs.empty())
         return;
     uint64_t mm = 0, hb = 0;
     stats_layout(jobs, &mm, &hb);
-    float* parts = nullptr;
+    Scratch<float> parts;
     if (phases & kPhaseMinmax)
     {
-        parts = static_cast<float*>(scratch_alloc(sizeof(float) * 2 * mm, s));
+        parts = Scratch<float>((size_t) (2 * mm), s);
         for (auto& j: jobs)
-            j.mm_part = parts + 2 * (int64_t) j.mm_block0;
+            j.mm_part = parts.get() + 2 * (int64_t) j.mm_block0;
     }
-    with_job_table(jobs, parts, s, [&](const StatsJob* dj, int n) {
-        launch_stats_table(dj, n, mm, hb, stats_walk(jobs.data(), n), phases, s, between);
-    });
+    const int n = (int) jobs.size();
+    auto dj     = Scratch<StatsJob>::upload(jobs, s);
+    launch_stats_table(dj.get(), n, mm, hb, stats_walk(jobs.data(), n), phases, s, between);
 }
 
 uint64_t channel_layout(std::vector<ChannelJob>& jobs, bool* any_hist)
@@ -1209,8 +1185,8 @@ void launch_channel_stats_many(std::vector<ChannelJob>& jobs, hipStream_t s)
         return;
     bool any_hist         = false;
     const uint64_t blocks = channel_layout(jobs, &any_hist);
-    with_job_table(jobs, nullptr, s,
-                   [&](const ChannelJob* dj, int n) { launch_channel_table(dj, n, blocks, any_hist, s); });
+    auto dj = Scratch<ChannelJob>::upload(jobs, s);
+    launch_channel_table(dj.get(), (int) jobs.size(), blocks, any_hist, s);
 }
 
 void launch_reset_table(const ResetJob* dj, int n, hipStream_t s)
@@ -1225,7 +1201,8 @@ void launch_reset_state_many(const std::vector<ResetJob>& jobs, hipStream_t s)
 {
     if (jobs.empty())
         return;
-    with_job_table(jobs, nullptr, s, [&](const ResetJob* dj, int n) { launch_reset_table(dj, n, s); });
+    auto dj = Scratch<ResetJob>::upload(jobs, s);
+    launch_reset_table(dj.get(), (int) jobs.size(), s);
 }
 
 // blockIdx.y = job; the workgroups along x stride over the job's 16-B words, then its tail bytes
@@ -1270,7 +1247,8 @@ void launch_zero_many(const std::vector<ZeroJob>& jobs, hipStream_t s)
     int64_t most = 0;
     for (const ZeroJob& j: jobs)
         most = std::max(most, j.bytes);
-    with_job_table(jobs, nullptr, s, [&](const ZeroJob* dj, int n) { launch_zero_table(dj, n, most, s); });
+    auto dj = Scratch<ZeroJob>::upload(jobs, s);
+    launch_zero_table(dj.get(), (int) jobs.size(), most, s);
 }
 
 void launch_reset_state(const TqDevice& d, int64_t C, hipStream_t s)

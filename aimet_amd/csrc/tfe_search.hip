@@ -11,11 +11,8 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
-#include <mutex>
 #include "tq_state.hpp"
 
-#include <mutex>
 #include <vector>
 
 namespace aimet_amd
@@ -276,9 +273,8 @@ void launch_kernel(const TfeJob& one, const TfeJob* jobs, int njobs, int64_t tot
         unsigned* tickets = ticket_alloc(s, (unsigned) total);
         if (tickets)
         {
-            auto* part = static_cast<uint64_t*>(scratch_alloc(sizeof(uint64_t) * 2 * total * splits, s));
-            launch_split(one, jobs, njobs, total, bw, sym, strict, unsign, splits, part, tickets, s);
-            scratch_free(part, s);
+            Scratch<uint64_t> part((size_t) (2 * total * splits), s);
+            launch_split(one, jobs, njobs, total, bw, sym, strict, unsign, splits, part.get(), tickets, s);
             return;
         }
     }
@@ -333,20 +329,6 @@ TfeJob job_of(const TqDevice& d, int64_t start)
     return TfeJob {d.pdf_init, d.hist_min, d.bucket_size, d.pdf, d.enc, start};
 }
 
-// Grow-only pinned host buffer per device for the batched searches' results (a D2H copy into
-// pageable memory is staged through the driver's bounce buffer: 0.56 ms for ResNet-50's 27,560
-// encodings, against ~0.01 ms pinned); held under the lock until the call has synchronised.
-struct PinnedOut
-{
-    std::mutex m;
-    void* p[64]    = {};
-    size_t cap[64] = {};
-};
-PinnedOut& pinned_out()
-{
-    static PinnedOut s;
-    return s;
-}
 }   // namespace
 
 void launch_tfe_search(const TqDevice& d, int64_t C, int bw, bool sym, bool strict, bool unsign, hipStream_t s)
@@ -366,56 +348,16 @@ void launch_tfe_search_many_to(const TqDevice* const* ds, const int64_t* Cs, int
         jobs[i] = job_of(*ds[i], total);
         total += Cs[i];
     }
-    auto* dout = static_cast<aimet_tf_encoding*>(scratch_alloc(sizeof(aimet_tf_encoding) * total, s));
+    Scratch<aimet_tf_encoding> dout((size_t) total, s);
     for (int i = 0; i < n; ++i)
-        jobs[i].out = dout + jobs[i].start;
+        jobs[i].out = dout.get() + jobs[i].start;
     const hipStream_t us = (prep != nullptr && prep != s) ? prep : s;
-    auto* djobs = static_cast<TfeJob*>(upload_async(jobs.data(), sizeof(TfeJob) * n, us));
+    auto djobs = Scratch<TfeJob>::upload(jobs.data(), (size_t) n, us, s);
     if (us != s)
         stream_join(s, us);   // the copy ran long before s gets here (the statistics passes)
-    launch_kernel(jobs[0], djobs, n, total, bw, sym, strict, unsign, s);
-    AIMET_HIP_CHECK(hipMemcpyAsync(pinned_dst, dout, sizeof(aimet_tf_encoding) * total, hipMemcpyDeviceToHost, s));
-    scratch_free(djobs, s);
-    scratch_free(dout, s);
-}
-
-void launch_tfe_search_many(const TqDevice* const* ds, const int64_t* Cs, int n, int bw, bool sym, bool strict,
-                            bool unsign, aimet_tf_encoding* host_out, hipStream_t s)
-{
-    if (n == 0)
-        return;
-    std::vector<TfeJob> jobs(n);
-    int64_t total = 0;
-    for (int i = 0; i < n; ++i)
-    {
-        jobs[i] = job_of(*ds[i], total);
-        total += Cs[i];
-    }
-    int dev = 0;
-    AIMET_HIP_CHECK(hipGetDevice(&dev));
-    AIMET_REQUIRE(dev >= 0 && dev < 64, "device id out of range");
-    auto* dout = static_cast<aimet_tf_encoding*>(scratch_alloc(sizeof(aimet_tf_encoding) * total, s));
-    for (int i = 0; i < n; ++i)
-        jobs[i].out = dout + jobs[i].start;
-    auto* djobs = static_cast<TfeJob*>(upload_async(jobs.data(), sizeof(TfeJob) * n, s));
-    launch_kernel(jobs[0], djobs, n, total, bw, sym, strict, unsign, s);
-    const size_t out_bytes = sizeof(aimet_tf_encoding) * total;
-    PinnedOut& po = pinned_out();
-    std::lock_guard<std::mutex> lock(po.m);
-    if (po.cap[dev] < out_bytes)
-    {
-        if (po.p[dev])
-            AIMET_HIP_CHECK(hipHostFree(po.p[dev]));
-        po.p[dev]   = nullptr;
-        po.cap[dev] = 0;
-        AIMET_HIP_CHECK(hipHostMalloc(&po.p[dev], out_bytes, hipHostMallocDefault));
-        po.cap[dev] = out_bytes;
-    }
-    AIMET_HIP_CHECK(hipMemcpyAsync(po.p[dev], dout, out_bytes, hipMemcpyDeviceToHost, s));
-    scratch_free(djobs, s);
-    scratch_free(dout, s);
-    AIMET_HIP_CHECK(hipStreamSynchronize(s));
-    std::memcpy(host_out, po.p[dev], out_bytes);
+    launch_kernel(jobs[0], djobs.get(), n, total, bw, sym, strict, unsign, s);
+    AIMET_HIP_CHECK(
+        hipMemcpyAsync(pinned_dst, dout.get(), sizeof(aimet_tf_encoding) * total, hipMemcpyDeviceToHost, s));
 }
 
 }   // namespace aimet_amd

@@ -160,14 +160,11 @@ int tfe_splits(int64_t total, bool sym);
 void launch_tfe_table(const TfeTable& t, int bw, bool sym, bool strict, bool unsign, hipStream_t s);
 // d.enc[c] <- TF-Enhanced encoding of channel c (statistics updated; see aimet_tq_get_encoding)
 void launch_tfe_search(const TqDevice& d, int64_t C, int bw, bool sym, bool strict, bool unsign, hipStream_t s);
-// the same for n quantizers in one launch; host_out <- their encodings concatenated
-// (sum of Cs). Synchronises s.
-void launch_tfe_search_many(const TqDevice* const* ds, const int64_t* Cs, int n, int bw, bool sym, bool strict,
-                            bool unsign, aimet_tf_encoding* host_out, hipStream_t s);
-// the same, asynchronous: the encodings are copied into pinned_dst (host-pinned, sum of Cs entries)
-// on s; the caller synchronises before reading it. `prep` (optional, another stream): the job
-// table's upload runs there, so it is done before s reaches the search (s waits for prep's work
-// enqueued so far) instead of adding a copy's latency between the statistics and the search
+// the same for n quantizers in one launch, asynchronous: their encodings concatenated (sum of Cs
+// entries) are copied into pinned_dst (host-pinned) on s; the caller synchronises before reading it.
+// `prep` (optional, another stream): the job table's upload runs there, so it is done before s
+// reaches the search (s waits for prep's work enqueued so far) instead of adding a copy's latency
+// between the statistics and the search
 void launch_tfe_search_many_to(const TqDevice* const* ds, const int64_t* Cs, int n, int bw, bool sym, bool strict,
                                bool unsign, aimet_tf_encoding* pinned_dst, hipStream_t s, hipStream_t prep = nullptr);
 // quantizer.cpp: `waiter` continues after everything enqueued on `from` so far (no host wait)

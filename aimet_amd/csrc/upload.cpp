@@ -84,6 +84,7 @@ struct ScratchCache
     std::vector<Block> free_blocks;
     std::vector<hipEvent_t> spare_events;
     std::unordered_map<void*, Live> live;
+    int64_t taken = 0;   // blocks handed out since the process began (aimet_scratch_taken)
 };
 ScratchCache& cache()
 {
@@ -95,7 +96,7 @@ constexpr size_t kMaxCachedBlocks = 64;
 
 }   // namespace
 
-void* scratch_alloc(size_t bytes, hipStream_t s)
+void* detail::scratch_alloc(size_t bytes, hipStream_t s)
 {
     if (bytes == 0)
         bytes = 1;
@@ -155,10 +156,11 @@ void* scratch_alloc(size_t bytes, hipStream_t s)
     }
     std::lock_guard<std::mutex> lock(c.m);
     c.live[d] = ScratchCache::Live {dev, real, mode};
+    ++c.taken;
     return d;
 }
 
-void scratch_free(void* p, hipStream_t s)
+void detail::scratch_free(void* p, hipStream_t s)
 {
     if (p == nullptr)
         return;
@@ -292,8 +294,8 @@ FoldBuffers fold_buffers(hipStream_t s, unsigned tickets, size_t part_floats)
         if (f.ticket == nullptr)
             return f;
     }
-    f.part    = static_cast<float*>(scratch_alloc(sizeof(float) * part_floats, s));
-    f.scratch = true;
+    f.own  = Scratch<float>(part_floats, s);
+    f.part = f.own.get();
     return f;
 }
 
@@ -306,17 +308,31 @@ size_t capture_pool_limit(size_t arena_floats)
     return prev;
 }
 
-void fold_buffers_release(const FoldBuffers& f, hipStream_t s)
+void scratch_live(int64_t* blocks, int64_t* bytes)
 {
-    if (f.scratch && f.part)
-        scratch_free(f.part, s);
+    ScratchCache& c = cache();
+    std::lock_guard<std::mutex> lock(c.m);
+    int64_t total = 0;
+    for (const auto& kv: c.live)
+        total += (int64_t) kv.second.bytes;
+    if (blocks)
+        *blocks = (int64_t) c.live.size();
+    if (bytes)
+        *bytes = total;
 }
 
-void* upload_async(const void* src, size_t bytes, hipStream_t s)
+int64_t scratch_taken()
 {
-    // a captured copy would re-read the (reused) pinned slot at every replay
-    AIMET_REQUIRE(s == nullptr || !capturing(s), "host tables cannot be uploaded inside a HIP-graph capture");
-    void* d = scratch_alloc(bytes, s);
+    ScratchCache& c = cache();
+    std::lock_guard<std::mutex> lock(c.m);
+    return c.taken;
+}
+
+namespace
+{
+// src -> the ring's next pinned slot -> d, on s
+void copy_through_ring(void* d, const void* src, size_t bytes, hipStream_t s)
+{
     Ring& r = ring(current_device());
     std::lock_guard<std::mutex> lock(r.m);
     Slot& slot = r.slots[r.next];
@@ -343,7 +359,16 @@ void* upload_async(const void* src, size_t bytes, hipStream_t s)
     std::memcpy(slot.host, src, bytes);
     AIMET_HIP_CHECK(hipMemcpyAsync(d, slot.host, bytes, hipMemcpyHostToDevice, s));
     AIMET_HIP_CHECK(hipEventRecord(slot.ev, s));
-    return d;
+}
+}   // namespace
+
+void* detail::upload_async(const void* src, size_t bytes, hipStream_t s)
+{
+    // a captured copy would re-read the (reused) pinned slot at every replay
+    AIMET_REQUIRE(s == nullptr || !capturing(s), "host tables cannot be uploaded inside a HIP-graph capture");
+    Scratch<char> block(bytes, s);   // back to the cache when the copy throws
+    copy_through_ring(block.get(), src, bytes, s);
+    return block.release();
 }
 
 }   // namespace aimet_amd

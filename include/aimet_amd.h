@@ -68,6 +68,13 @@ int aimet_device_count(void);
  * fold); *previous = the cap before. A launch captured once the arena is used up takes the same
  * fold as a launch of its own instead: the same values. For tests of that fallback. */
 int aimet_capture_pool_limit(int64_t arena_floats, int64_t* previous);
+/* Temporary device blocks that the library has handed out to its own calls and not yet taken back
+ * (either pointer may be null). Every entry point takes back what it took before it returns, so
+ * between calls both are zero; a count that grows is a device-memory leak. For tests. */
+int aimet_scratch_live(int64_t* blocks, int64_t* bytes);
+/* Temporary device blocks handed out since the process began, taken back or not: the difference
+ * across a call says how many that call used. For tests that a call took the path they mean. */
+int aimet_scratch_taken(int64_t* blocks);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Encoding math (host, exact reference arithmetic)                                            */

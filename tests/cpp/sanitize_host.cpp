@@ -178,6 +178,10 @@ static void device_lifecycle()
             CHECK(aimet_tq_destroy(q));
         for (auto* q: pc)
             CHECK(aimet_tq_destroy(q));
+        // every call above handed back the scratch blocks and job tables it took
+        int64_t live = -1;
+        CHECK(aimet_scratch_live(&live, nullptr));
+        CHECK(live == 0 ? AIMET_OK : 1);
     }
     CHECK(hipDeviceSynchronize() == hipSuccess ? AIMET_OK : 1);
     (void) hipFree(x);
