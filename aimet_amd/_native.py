@@ -277,6 +277,11 @@ _PROTOTYPES = {
     "aimet_attn_softmax": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _vp, _enc_p, _enc_p, _vp],
     "aimet_attn_softmax_max_s": [],
     "aimet_attn_launch_count": [_i64p, _int],
+    "aimet_lora_merge": [_vp, _vp, _vp, _i64, _int, _enc_p, _enc_p, _enc_p, _vp],
+    "aimet_lora_merge_backward": [_vp, _vp, _vp, _vp, _vp, _i64, _int, _enc_p, _enc_p, _enc_p, _vp],
+    "aimet_lora_scale": [_vp, _vp, _i64, _int, ctypes.c_float, _enc_p, _enc_p, _vp],
+    "aimet_lora_scale_backward": [_vp, _vp, _vp, _i64, _int, ctypes.c_float, _enc_p, _enc_p, _vp],
+    "aimet_lora_launch_count": [_i64p, _int],
 }
 _RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p,
              "aimet_attn_softmax_max_s": ctypes.c_int64}

@@ -1,5 +1,5 @@
 """Functional operations as modules, so that QuantizationSimModel can give them quantizers
-(aimet_torch.v1.nn.modules.custom: Add, Divide, MatMul), and the tuple of module types a transformer
+(aimet_torch.v1.nn.modules.custom: Add, Multiply, Divide, MatMul), and the tuple of module types a transformer
 needs wrapped.
 
     sim = QuantizationSimModel(model, dummy_input, quantizable_types=TRANSFORMER_QUANTIZABLE_TYPES)
@@ -18,6 +18,14 @@ class Add(nn.Module):
     @staticmethod
     def forward(x, y):
         return x + y
+
+
+class Multiply(nn.Module):
+    """x * y (y a tensor or a number)."""
+
+    @staticmethod
+    def forward(x, y):
+        return x * y
 
 
 class Divide(nn.Module):

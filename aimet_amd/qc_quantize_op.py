@@ -526,6 +526,16 @@ class StaticGridQuantWrapper(QcQuantizeWrapper):
 
     def forward(self, *inputs, **kwargs):
         """v1/qc_quantize_op.py:705-745."""
+        wrapped_output = self.forward_raw(*inputs, **kwargs)
+        if not isinstance(wrapped_output, (list, tuple)):
+            wrapped_output = [wrapped_output]
+        output = self._quantize_activation(self.output_quantizers, list(wrapped_output))
+        return output[0] if len(output) == 1 else output
+
+    def forward_raw(self, *inputs, **kwargs):
+        """forward() without the output quantizers: the wrapped module's raw output, for a caller that
+        applies the output quantizer in a kernel of its own (aimet_amd.peft; output_quantizer_fusable,
+        fused_output_encoding)."""
         ran = self.__dict__.get("_analysis_ran")   # QuantizationSimModel.compute_encodings is watching
         if ran is not None:
             ran[0] = True
@@ -541,10 +551,7 @@ class StaticGridQuantWrapper(QcQuantizeWrapper):
         # per ResNet-50 bs256 forward) changes nothing
         wrapped_output = self._module_to_wrap(*quantized_inputs, **kwargs)
         self._restore_shadow_params(shadow_params)
-        if not isinstance(wrapped_output, (list, tuple)):
-            wrapped_output = [wrapped_output]
-        output = self._quantize_activation(self.output_quantizers, list(wrapped_output))
-        return output[0] if len(output) == 1 else output
+        return wrapped_output
 
     def _restore_shadow_params(self, shadow_params):
         for name, param in self.get_named_parameters():
@@ -656,8 +663,15 @@ class StaticGridQuantWrapper(QcQuantizeWrapper):
         the output quantizer: nothing but output quantizer 0 would act in the forward (no enabled
         input or parameter quantizer), and that one is disabled or a per-tensor integer static-grid
         quantizer rounding to nearest."""
-        if len(self.output_quantizers) != 1 or any(q.enabled for q in self.input_quantizers) or \
-                any(q.enabled for q in self.param_quantizers.values()):
+        if any(q.enabled for q in self.input_quantizers) or any(q.enabled for q in self.param_quantizers.values()):
+            return False
+        return self.output_quantizer_fusable()
+
+    def output_quantizer_fusable(self) -> bool:
+        """The output-quantizer half of output_fusable(), for a caller that runs the inputs and the
+        parameters through forward_raw(): exactly one output quantizer, disabled or a per-tensor
+        integer static-grid quantizer rounding to nearest."""
+        if len(self.output_quantizers) != 1:
             return False
         q = self.output_quantizers[0]
         if not q.enabled:

@@ -1054,6 +1054,37 @@ int64_t aimet_attn_softmax_max_s(void);
 /* Kernel launches aimet_attn_softmax has issued in this process; reset != 0 zeroes it. */
 int aimet_attn_launch_count(int64_t* count, int reset);
 
+/* ---- PEFT LoRA adapters in QuantSim (aimet_torch/peft.py LoraLayer) -------------------------------
+ * The element-wise tail of an adapted layer, one launch each, equal bit for bit to the wrapped children
+ * called one by one (csrc/lora.hip states every rounding). All tensors of a call hold n elements of one
+ * dtype: io_dtype 0 = float32, 1 = float16, 2 = bfloat16 (the 16-bit values as in
+ * aimet_qdq_per_tensor_16). An encoding is a host struct of which min, max and bw are read; NULL: that
+ * quantizer is disabled (identity going forward, mask 1 going back). An output may not overlap an
+ * input or another output: AIMET_ERR_INVALID_ARGUMENT, nothing launched.
+ *
+ * out = Q_out([Q_u(u) + Q_v(v)]_T): base_layer's and lora_B's output quantizers, the add and
+ * add_lora_to_res' output quantizer; [.]_T rounds to the I/O dtype. */
+int aimet_lora_merge(const void* u, const void* v, void* out, int64_t n, int io_dtype, const aimet_tf_encoding* enc_u,
+                     const aimet_tf_encoding* enc_v, const aimet_tf_encoding* enc_out, void* stream);
+/* The straight-through gradients of aimet_lora_merge: with s = [Q_u(u) + Q_v(v)]_T recomputed,
+ * g1 = grad * (min_out <= s <= max_out), grad_u = g1 * (min_u <= u <= max_u),
+ * grad_v = g1 * (min_v <= v <= max_v); the bounds are the encodings' raw min / max rounded to float32
+ * and then to the I/O dtype. grad_u or grad_v may be NULL (nothing is written for it). */
+int aimet_lora_merge_backward(const void* u, const void* v, const void* grad, void* grad_u, void* grad_v, int64_t n,
+                              int io_dtype, const aimet_tf_encoding* enc_u, const aimet_tf_encoding* enc_v,
+                              const aimet_tf_encoding* enc_out, void* stream);
+/* out = Q_out([Q_a(a) * scale]_T): lora_A's output quantizer, mul_scale and its output quantizer. For
+ * 16-bit I/O the caller passes the scale already rounded to the I/O dtype (csrc/lora.hip: the rule). */
+int aimet_lora_scale(const void* a, void* out, int64_t n, int io_dtype, float scale, const aimet_tf_encoding* enc_a,
+                     const aimet_tf_encoding* enc_out, void* stream);
+/* grad_a = ((grad * m_out) * scale) * m_a, m_out = (min_out <= [Q_a(a) * scale]_T <= max_out),
+ * m_a = (min_a <= a <= max_a), each product rounded to the I/O dtype. */
+int aimet_lora_scale_backward(const void* a, const void* grad, void* grad_a, int64_t n, int io_dtype, float scale,
+                              const aimet_tf_encoding* enc_a, const aimet_tf_encoding* enc_out, void* stream);
+/* Calls of the four entry points above that launched on the GPU in this process (a call is one launch,
+ * plus one for a ragged tail); reset != 0 zeroes it. */
+int aimet_lora_launch_count(int64_t* count, int reset);
+
 #ifdef __cplusplus
 }
 #endif
