@@ -23,6 +23,7 @@
 #include "fast_pow.hpp"
 #include "recon.hpp"
 #include "sleef_pow.hpp"
+#include "stream_map.hpp"   // aligned16
 
 #include <atomic>
 
@@ -743,11 +744,6 @@ struct LossFold
         AIMET_LAUNCH_CHECK();
     }
 };
-
-bool aligned16(const void* p)
-{
-    return (reinterpret_cast<uintptr_t>(p) & 15) == 0;
-}
 
 // the rounding loss's pow for launches from now on: the fast pow (0, default) or the bit-exact
 // emulation of torch's (1); aimet_adaround_set_exact_pow

@@ -1,5 +1,6 @@
 """Time aimet_adaround_dw_step on MobileNet-v2's depthwise shapes (batch 32 drawn from 1024 cached
-rows) by HIP events; AIMET_TUNE_DW_U / AIMET_TUNE_DW_PER select the variant (tuning only).
+rows) by HIP events. The label tags the output lines, e.g. with the build that was timed (the
+tuning switches behind the variants of profiles/r03/dw_step_tune.jsonl are gone from the library).
 usage: python tools/studies/dw_step_tune.py [label]"""
 import ctypes
 import json
