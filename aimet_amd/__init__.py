@@ -15,6 +15,8 @@ operator surface on top:
 * ``aimet_amd.batch_norm_fold``, ``aimet_amd.cross_layer_equalization``, ``aimet_amd.bias_correction``
                                    -- data-free quantization: BN fold, CLS + high-bias fold, bias correction
 * ``aimet_amd.quant_analyzer``     -- QuantAnalyzer: sensitivity, ranges, histograms, per-layer MSE on a fused kernel
+* ``aimet_amd.mixed_precision``, ``aimet_amd.amp``
+                                   -- automatic mixed precision: greedy per-group bitwidths, SQNR callback on a fused kernel
 * ``aimet_amd.transformers``, ``aimet_amd.elementwise_ops``
                                    -- quantizable MultiheadAttention / transformer layers on a fused softmax kernel
 * ``aimet_amd.distributed``        -- calibration sharded over ranks (RCCL stats exchange)

@@ -266,6 +266,8 @@ _PROTOTYPES = {
     "aimet_bc_launch_count": [_i64p, _int],
     "aimet_qa_sq_err": [_vp, _vp, _i64, _int, ctypes.c_double, _vp, _vp],
     "aimet_qa_launch_count": [_i64p, _int],
+    "aimet_amp_sqnr_add": [_vp, _vp, _i64, _int, ctypes.c_double, _vp, _vp],
+    "aimet_amp_launch_count": [_i64p, _int],
     "aimet_bnre_forward": [_vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp],
     "aimet_bnre_forward_form": [_int, ctypes.POINTER(_int)],
     "aimet_bnre_finish": [ctypes.POINTER(BnreFinishJobC), _i64, _vp],

@@ -12,6 +12,14 @@
 //    consecutive partials in index order, then a fixed tree), multiplies by scale once and adds into
 //    acc. No atomics: the order of every addition is fixed by n, the dtype and the two base
 //    alignments, so two runs on the same pointers give the same bits.
+//
+//  * aimet_amp_sqnr_add: acc[0] += (sum ref_i^2 / n) / (sum (ref_i - x_i)^2 / n + eps), the per-batch
+//    ratio of mixed precision's SQNR callback (aimet_torch/amp/mixed_precision_algo.py _compute_sqnr;
+//    the reference clones, subtracts, squares twice, takes two means and reads the ratio back). The
+//    same first launch; its fold also takes the two means, the ratio and the add, so a batch costs
+//    one read of each tensor and an evaluation one read-back.
+
+#include <limits>
 
 #include "common.hpp"
 #include "io16.hpp"
@@ -25,7 +33,8 @@ constexpr int kQaBlock          = 256;
 constexpr int64_t kQaVecPerLane = 2;   // 16-byte loads per input a lane has before the grid grows no further
 constexpr int64_t kQaMaxElems   = int64_t(1) << 40;
 
-LaunchCounter g_launches;
+LaunchCounter g_launches;       // aimet_qa_sq_err
+LaunchCounter g_amp_launches;   // aimet_amp_sqnr_add
 
 // Fixed-shape tree over the workgroup's 256 pairs; every lane returns with lds[0], lds[kQaBlock] the sums.
 __device__ __forceinline__ void block_sum2(double a, double b, double* lds)
@@ -173,8 +182,33 @@ __global__ __launch_bounds__(kQaBlock) void qa_fold_kernel(const double* __restr
     }
 }
 
+// acc[0] += (S / n) / (N / n + eps) over the same partials, N = sum (ref - x)^2 and S = sum ref^2: the
+// fold of qa_fold_kernel, then two means, the ratio and the add, each rounded once
+__global__ __launch_bounds__(kQaBlock) void amp_sqnr_fold_kernel(const double* __restrict__ part, int64_t nparts,
+                                                                 int64_t per, double n, double eps,
+                                                                 double* __restrict__ acc)
+{
+    __shared__ double lds[2 * kQaBlock];
+    const int64_t lo = (int64_t) threadIdx.x * per;
+    const int64_t hi = lo + per < nparts ? lo + per : nparts;
+    double d = 0.0, q = 0.0;
+    for (int64_t k = lo; k < hi; ++k)
+    {
+        d = d + part[2 * k];
+        q = q + part[2 * k + 1];
+    }
+    block_sum2(d, q, lds);
+    if (threadIdx.x == 0)
+    {
+        const double noise = lds[0] / n, signal = lds[kQaBlock] / n;
+        acc[0] = acc[0] + signal / (noise + eps);
+    }
+}
+
+// The first launch of both entry points: a workgroup's (sum (ref - x)^2, sum ref^2) into part[2 * b ..].
+// Returns the number of workgroups.
 template <int IO>
-void launch_sq_err(const void* ref_v, const void* x_v, int64_t n, double scale, double* acc, hipStream_t s)
+int64_t launch_partials(const void* ref_v, const void* x_v, int64_t n, Scratch<double>& part, hipStream_t s)
 {
     using T           = typename Elem<IO>::type;
     constexpr int EPV = 16 / (int) sizeof(T);
@@ -182,7 +216,6 @@ void launch_sq_err(const void* ref_v, const void* x_v, int64_t n, double scale, 
     const T* x        = static_cast<const T*>(x_v);
     const uintptr_t ra = reinterpret_cast<uintptr_t>(ref) & 15, xa = reinterpret_cast<uintptr_t>(x) & 15;
     int64_t blocks;
-    Scratch<double> part;
     if (ra == xa)
     {
         const int64_t head = std::min<int64_t>((int64_t) (((16 - ra) & 15) / sizeof(T)), n);
@@ -198,9 +231,34 @@ void launch_sq_err(const void* ref_v, const void* x_v, int64_t n, double scale, 
         qa_sq_err_elem_kernel<IO><<<(unsigned) blocks, kQaBlock, 0, s>>>(ref, x, n, part.get());
     }
     AIMET_LAUNCH_CHECK();
-    qa_fold_kernel<<<1, kQaBlock, 0, s>>>(part.get(), blocks, ceil_div(blocks, kQaBlock), scale, acc);
-    AIMET_LAUNCH_CHECK();
-    g_launches.add(2);
+    return blocks;
+}
+
+int64_t launch_partials(int io_dtype, const void* ref, const void* x, int64_t n, Scratch<double>& part, hipStream_t s)
+{
+    switch (io_dtype)
+    {
+    case IO_F32: return launch_partials<IO_F32>(ref, x, n, part, s);
+    case IO_F16: return launch_partials<IO_F16>(ref, x, n, part, s);
+    default: return launch_partials<IO_BF16>(ref, x, n, part, s);
+    }
+}
+
+// what both entry points ask of their arguments
+void require_pair(const void* ref, const void* x, int64_t n, int io_dtype, const double* acc_dev, const char* what)
+{
+    const std::string w(what);
+    AIMET_REQUIRE(n > 0 && n <= kQaMaxElems, (w + ": n must be in 1 .. 2^40").c_str());
+    AIMET_REQUIRE(io_dtype == IO_F32 || io_dtype == IO_F16 || io_dtype == IO_BF16,
+                  (w + ": io_dtype is 0 (float32), 1 (float16) or 2 (bfloat16)").c_str());
+    require_device_ptr(ref, (w + " reference").c_str());
+    require_device_ptr(x, (w + " input").c_str());
+    require_device_ptr(acc_dev, (w + " accumulator").c_str());
+    const uintptr_t elem = io_dtype == IO_F32 ? 4 : 2;
+    AIMET_REQUIRE((reinterpret_cast<uintptr_t>(ref) & (elem - 1)) == 0 &&
+                      (reinterpret_cast<uintptr_t>(x) & (elem - 1)) == 0 &&
+                      (reinterpret_cast<uintptr_t>(acc_dev) & 7) == 0,
+                  (w + ": misaligned pointer").c_str());
 }
 
 }   // namespace
@@ -213,25 +271,34 @@ extern "C" {
 int aimet_qa_sq_err(const void* ref, const void* x, int64_t n, int io_dtype, double scale, double* acc_dev, void* stream)
 {
     return guarded([&] {
-        AIMET_REQUIRE(n > 0 && n <= kQaMaxElems, "squared error: n must be in 1 .. 2^40");
-        AIMET_REQUIRE(io_dtype == IO_F32 || io_dtype == IO_F16 || io_dtype == IO_BF16,
-                      "squared error: io_dtype is 0 (float32), 1 (float16) or 2 (bfloat16)");
-        require_device_ptr(ref, "squared error reference");
-        require_device_ptr(x, "squared error input");
-        require_device_ptr(acc_dev, "squared error accumulator");
-        const uintptr_t elem = io_dtype == IO_F32 ? 4 : 2;
-        AIMET_REQUIRE((reinterpret_cast<uintptr_t>(ref) & (elem - 1)) == 0 &&
-                          (reinterpret_cast<uintptr_t>(x) & (elem - 1)) == 0 &&
-                          (reinterpret_cast<uintptr_t>(acc_dev) & 7) == 0,
-                      "squared error: misaligned pointer");
+        require_pair(ref, x, n, io_dtype, acc_dev, "squared error");
         hipStream_t s = as_stream(stream);
-        switch (io_dtype)
-        {
-        case IO_F32: launch_sq_err<IO_F32>(ref, x, n, scale, acc_dev, s); break;
-        case IO_F16: launch_sq_err<IO_F16>(ref, x, n, scale, acc_dev, s); break;
-        default: launch_sq_err<IO_BF16>(ref, x, n, scale, acc_dev, s); break;
-        }
+        Scratch<double> part;
+        const int64_t blocks = launch_partials(io_dtype, ref, x, n, part, s);
+        qa_fold_kernel<<<1, kQaBlock, 0, s>>>(part.get(), blocks, ceil_div(blocks, kQaBlock), scale, acc_dev);
+        AIMET_LAUNCH_CHECK();
+        g_launches.add(2);
     });
+}
+
+int aimet_amp_sqnr_add(const void* ref, const void* x, int64_t n, int io_dtype, double eps, double* acc_dev, void* stream)
+{
+    return guarded([&] {
+        require_pair(ref, x, n, io_dtype, acc_dev, "SQNR");
+        AIMET_REQUIRE(eps >= 0.0 && eps < std::numeric_limits<double>::infinity(), "SQNR: eps must be finite and >= 0");
+        hipStream_t s = as_stream(stream);
+        Scratch<double> part;
+        const int64_t blocks = launch_partials(io_dtype, ref, x, n, part, s);
+        amp_sqnr_fold_kernel<<<1, kQaBlock, 0, s>>>(part.get(), blocks, ceil_div(blocks, kQaBlock), (double) n, eps,
+                                                    acc_dev);
+        AIMET_LAUNCH_CHECK();
+        g_amp_launches.add(2);
+    });
+}
+
+int aimet_amp_launch_count(int64_t* count, int reset)
+{
+    return guarded([&] { g_amp_launches.read(count, reset); });
 }
 
 int aimet_qa_launch_count(int64_t* count, int reset)

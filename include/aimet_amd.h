@@ -909,6 +909,20 @@ int aimet_qa_sq_err(const void* ref, const void* x, int64_t n, int io_dtype, dou
 /* Kernel launches aimet_qa_sq_err has issued in this process; reset != 0 zeroes it. */
 int aimet_qa_launch_count(int64_t* count, int reset);
 
+/* ---- Automatic mixed precision (aimet_torch/amp/mixed_precision_algo.py _compute_sqnr) -------------
+ * acc_dev[0] += (S / n) / (N / n + eps), S = sum_i ((double) ref[i])^2 and
+ * N = sum_i ((double) ref[i] - (double) x[i])^2: one batch's signal-to-noise ratio as the SQNR eval
+ * callback sums it (the reference's eps is 1e-4), in double. n, io_dtype, the alignment rules and the
+ * vector / element route are those of aimet_qa_sq_err, and the per-workgroup partial sums are the same
+ * kernels; the second launch folds them in a fixed order, takes the two means, the ratio and the
+ * add, each rounded once. eps finite and >= 0. One read of each tensor, two launches, no atomics, so
+ * equal pointers and sizes give equal bits. x == ref gives mean(ref^2) / eps. */
+int aimet_amp_sqnr_add(const void* ref, const void* x, int64_t n, int io_dtype, double eps, double* acc_dev,
+                       void* stream);
+
+/* Kernel launches aimet_amp_sqnr_add has issued in this process; reset != 0 zeroes it. */
+int aimet_amp_launch_count(int64_t* count, int reset);
+
 /* ---- BatchNorm re-estimation and BN fold to scale (aimet_torch/bn_reestimation.py,
  * batch_norm_fold.py fold_all_batch_norms_to_scale) ------------------------------------------------
  * Device pointers throughout. No atomics: the order of every addition is fixed by the sizes and the
