@@ -284,6 +284,9 @@ _PROTOTYPES = {
     "aimet_lora_scale": [_vp, _vp, _i64, _int, ctypes.c_float, _enc_p, _enc_p, _vp],
     "aimet_lora_scale_backward": [_vp, _vp, _vp, _i64, _int, ctypes.c_float, _enc_p, _enc_p, _vp],
     "aimet_lora_launch_count": [_i64p, _int],
+    "aimet_bq_encode_qdq": [_vp, _vp, _i64, _i64, _i64, _int, _i32, _int, _int, _int, _int, _vp, _vp, _vp, _vp],
+    "aimet_bq_row_path": [_i64, _i64, _int, ctypes.POINTER(_int)],
+    "aimet_bq_launch_count": [_i64p, _int],
 }
 _RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p,
              "aimet_attn_softmax_max_s": ctypes.c_int64}

@@ -381,10 +381,7 @@ aimet_tf_encoding entropy_encoding_from_range(float kl_lo, float kl_hi, int32_t 
 
 aimet_tf_encoding tf_encoding(double accMin, double accMax, int32_t bw, bool sym, bool strict, bool unsign)
 {
-    double lo = std::min(0.0, accMin);
-    double hi = std::max(0.0, accMax);
-    hi        = std::max(hi, lo + kMinRange);
-    return computed_encoding(bw, lo, hi, sym, strict, unsign);
+    return mse::tf_encoding(accMin, accMax, bw, sym, strict, unsign);   // shared with the device (blockwise.hip)
 }
 
 aimet_tf_encoding histogram_encoding(int scheme, bool initialized, bool stats_updated, float hist_min,

@@ -58,6 +58,16 @@ AIMET_HD inline aimet_tf_encoding computed_encoding(int bw, double mn, double mx
     return e;
 }
 
+// TfEncodingAnalyzer::computeEncoding (TfEncodingAnalyzer.cpp:80-101) from the accumulated min / max:
+// zero inside the range, a range of at least 0.01, then getComputedEncodings
+AIMET_HD inline aimet_tf_encoding tf_encoding(double accMin, double accMax, int bw, bool sym, bool strict, bool unsign)
+{
+    double lo = tfe::smin(0.0, accMin);
+    double hi = tfe::smax(0.0, accMax);
+    hi        = tfe::smax(hi, lo + 0.01);
+    return computed_encoding(bw, lo, hi, sym, strict, unsign);
+}
+
 // Candidate grid of _minimizeMSE (:137-200): every bucket edge inside the observed range splits
 // into the negative mins and positive maxs (+ 0 each); bin centres carry the PDF mass.
 struct Setup

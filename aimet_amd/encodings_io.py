@@ -90,6 +90,8 @@ def export_quantizer_encoding(quantizer) -> Optional[List[Dict]]:
     """v1/qc_quantize_op.py:1529-1545."""
     if not quantizer.enabled:
         return None
+    if hasattr(quantizer, "export_encodings"):   # a blockwise quantizer: from its device table
+        return quantizer.export_encodings()
     encoding = get_encoding_by_quantizer(quantizer)
     if isinstance(encoding, list):
         return [create_encoding_dict(e, quantizer, False) for e in encoding]

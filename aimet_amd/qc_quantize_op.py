@@ -405,6 +405,11 @@ class QcQuantizeWrapper(nn.Module):
                     raise RuntimeError("The quantsim passed for loading encodings does not have the same "
                                        "configuration as the quantsim which was used to export the encodings")
                 continue
+            if hasattr(q, "import_encodings"):   # a blockwise quantizer restores its device table
+                q.import_encodings(encoding)
+                if not allow_overwrite:
+                    q.freeze_encoding()
+                continue
             per_channel = isinstance(q, StaticGridPerChannelQuantizer)
             if encoding[0]["dtype"] == "float":
                 pass   # {"bitwidth", "dtype"} only (one entry, whatever the channel count): the quantizer stays
@@ -737,7 +742,9 @@ class SteGatingFuncForParameters(torch.autograd.Function):
             if q.bitwidth == 32 or q.data_type == QuantizationDataType.float:
                 continue
             if q.enabled and param.grad is not None and q.encoding is not None:
-                if isinstance(q.encoding, list):
+                if hasattr(q, "ste_backward"):   # a blockwise quantizer: its own [1, E, BL] view
+                    param.grad = q.ste_backward(param, param.grad)
+                elif isinstance(q.encoding, list):
                     param.grad = compute_dloss_by_dx(param, param.grad, [e.min for e in q.encoding],
                                                      [e.max for e in q.encoding], q._ch_axis)
                 else:

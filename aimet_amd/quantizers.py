@@ -565,7 +565,7 @@ def compute_encodings_batched(quantizers):
     groups = {}
     for q in quantizers:
         if not q.enabled or q._is_encoding_frozen or q.bitwidth == 32 or \
-                q.data_type == QuantizationDataType.float:
+                q.data_type == QuantizationDataType.float or getattr(q, "computes_own_encoding", False):
             q.compute_encoding()           # the non-native branches
             continue
         key = (int(q.bitwidth), bool(q.use_symmetric_encodings), bool(q.use_strict_symmetric),

@@ -1099,6 +1099,34 @@ int aimet_lora_scale_backward(const void* a, const void* grad, void* grad_a, int
  * plus one for a ragged tail); reset != 0 zeroes it. */
 int aimet_lora_launch_count(int64_t* count, int reset);
 
+/* ---- Blockwise and LPBQ weight quantization (csrc/blockwise.hip) -----------------------------------
+ * One launch over a contiguous weight viewed as [R][NB][BL]: R output channels, NB blocks a row, BL
+ * contiguous elements a block (block_size x kh kw with the block along the input features); E = R NB
+ * encodings in [channel][block] order. io_dtype 0 = float32, 1 = float16, 2 = bfloat16. Per block:
+ *   min / max of its elements (float32 compares), the TF analyzer's encoding of them in double
+ *   (zero inside the range, a range of at least 0.01, getComputedEncodings with the three flags);
+ *   scale_bitwidth s > 0 (LPBQ, symmetric only): factor[r] = max_b delta / 2^s,
+ *     q[e] = clip(rint(delta / factor[r]), 1, 2^s) (half to even), delta = q[e] factor[r],
+ *     min = delta offset, max = (2^bw - 1 + offset) delta; q and factor are written only then;
+ *   table[k E + e] = (float) {min, max, delta, offset}[k], the layout aimet_qdq_per_channel,
+ *     aimet_qdq_per_channel_16 and aimet_ste_backward{,_16} take with outer = 1, C = E, K = BL;
+ *   out (may be NULL: encodings only; may be in; may not overlap it otherwise) = the nearest-rounding
+ *     quantize-dequantize of the block with its table column, 16-bit outputs rounded once.
+ * Pointers need the alignment of their element type only. NB above AIMET_BQ_MAX_BLOCKS is
+ * AIMET_ERR_INVALID_ARGUMENT and nothing is written. */
+#define AIMET_BQ_MAX_BLOCKS 1024
+int aimet_bq_encode_qdq(const void* in, void* out, int64_t R, int64_t NB, int64_t BL, int io_dtype, int32_t bw,
+                        int use_symmetric, int use_strict_symmetric, int use_unsigned_symmetric, int scale_bitwidth,
+                        float* table, int32_t* q, double* factor, void* stream);
+/* Where aimet_bq_encode_qdq keeps a row of this shape between its two phases (in and out congruent
+ * mod 16): in a wave's registers, in a workgroup's LDS, or nowhere (the row is read twice). */
+#define AIMET_BQ_PATH_WAVE 0
+#define AIMET_BQ_PATH_GROUP 1
+#define AIMET_BQ_PATH_TWO_PASS 2
+int aimet_bq_row_path(int64_t NB, int64_t BL, int io_dtype, int* path);
+/* Kernel launches aimet_bq_encode_qdq has issued in this process; reset != 0 zeroes it. */
+int aimet_bq_launch_count(int64_t* count, int reset);
+
 #ifdef __cplusplus
 }
 #endif
