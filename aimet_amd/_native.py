@@ -7,7 +7,7 @@ import ctypes
 import os
 import subprocess
 
-import torch  # noqa: F401  -- load torch's HIP runtime first so libaimet_amd binds to the same one
+import torch  # load torch's HIP runtime first so libaimet_amd binds to the same one
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libaimet_amd.so")
@@ -292,6 +292,17 @@ _RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char
              "aimet_attn_softmax_max_s": ctypes.c_int64}
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
+
+# csrc/io16.hpp's IoType: the io_dtype argument of every entry point that also takes 16-bit tensors
+IO_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def io_code(dtype, error, text):
+    """IO_CODES[dtype]; any other dtype raises the caller's own error(text % dtype)."""
+    if dtype not in IO_CODES:
+        raise error(text % dtype)
+    return IO_CODES[dtype]
+
 
 _lib = None
 _load_error = None

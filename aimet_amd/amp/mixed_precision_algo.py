@@ -46,7 +46,6 @@ _logger = logging.getLogger("aimet_amd.amp")
 
 SQNR_EPS = 1e-4                 # the reference's _compute_sqnr
 LAUNCHES_PER_BATCH = 2          # aimet_amp_sqnr_add: the partial sums and their fold
-_IO_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}   # aimet_amp_sqnr_add's io_dtype
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -63,7 +62,7 @@ def add_sqnr(ref: torch.Tensor, x: torch.Tensor, acc: torch.Tensor, eps: float =
     """acc[0] += mean(ref^2) / (mean((ref - x)^2) + eps) (aimet_amp_sqnr_add): ref and x contiguous
     device tensors of one shape and dtype (float32 / float16 / bfloat16), acc one float64 on the
     same device."""
-    if ref.shape != x.shape or ref.dtype != x.dtype or ref.dtype not in _IO_DTYPES:
+    if ref.shape != x.shape or ref.dtype != x.dtype or ref.dtype not in _native.IO_CODES:
         raise ValueError("SQNR: needs two float32 / float16 / bfloat16 tensors of one shape and dtype")
     if not (ref.is_cuda and x.is_cuda and acc.is_cuda) or not (ref.is_contiguous() and x.is_contiguous()):
         raise ValueError("SQNR: needs contiguous device tensors; the MI355X core has no CPU path")
@@ -71,7 +70,7 @@ def add_sqnr(ref: torch.Tensor, x: torch.Tensor, acc: torch.Tensor, eps: float =
         raise ValueError("SQNR: the accumulator is one float64")
     with torch.cuda.device(ref.device):
         _native.call("aimet_amp_sqnr_add", ctypes.c_void_p(ref.data_ptr()), ctypes.c_void_p(x.data_ptr()), ref.numel(),
-                     _IO_DTYPES[ref.dtype], float(eps), ctypes.c_void_p(acc.data_ptr()),
+                     _native.IO_CODES[ref.dtype], float(eps), ctypes.c_void_p(acc.data_ptr()),
                      ctypes.c_void_p(torch.cuda.current_stream(ref.device).cuda_stream))
 
 
@@ -93,7 +92,7 @@ def _staged(output, device) -> torch.Tensor:
     if not isinstance(output, torch.Tensor):
         raise ValueError("SQNR: the forward pass was expected to return a torch.Tensor, but returned %s; give "
                          "EvalCallbackFactory a forward_fn that adapts the output" % type(output))
-    if output.dtype not in _IO_DTYPES:
+    if output.dtype not in _native.IO_CODES:
         raise ValueError("SQNR: the model output is %s; float32, float16 and bfloat16 are supported" % output.dtype)
     return output.detach().to(device).contiguous()
 

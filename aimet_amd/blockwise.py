@@ -26,10 +26,7 @@ from torch import nn
 from aimet_amd import _native
 from aimet_amd.libpymo import RoundingMode, TfEncoding
 from aimet_amd.quantizers import (QuantizationDataType, StaticGridTensorQuantizer, _round_mode, compute_dloss_by_dx)
-from aimet_amd.tensor_quantizer import IO_DTYPES, qdq_per_channel_table
-
-_IO_CODES = dict(IO_DTYPES)
-_IO_CODES[torch.float32] = 0
+from aimet_amd.tensor_quantizer import qdq_per_channel_table
 
 PATH_WAVE, PATH_GROUP, PATH_TWO_PASS = 0, 1, 2
 
@@ -44,7 +41,7 @@ def launch_count(reset: bool = False) -> int:
 def row_path(NB: int, BL: int, dtype=torch.float32) -> int:
     """Where the kernel keeps a row of NB blocks of BL elements: PATH_WAVE, PATH_GROUP or PATH_TWO_PASS."""
     p = ctypes.c_int(0)
-    _native.call("aimet_bq_row_path", int(NB), int(BL), _IO_CODES[dtype], ctypes.byref(p))
+    _native.call("aimet_bq_row_path", int(NB), int(BL), _native.IO_CODES[dtype], ctypes.byref(p))
     return p.value
 
 
@@ -56,8 +53,8 @@ def encode_qdq(t: torch.Tensor, R: int, NB: int, BL: int, bitwidth: int, symmetr
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise RuntimeError("aimet_amd: blockwise quantization computes its encodings on the HIP device the weight "
                            "is on; there is no CPU path")
-    if t.dtype not in _IO_CODES:
-        raise TypeError("blockwise quantization takes float32, float16 or bfloat16 weights (got %s)" % t.dtype)
+    code = _native.io_code(t.dtype, TypeError, "blockwise quantization takes float32, float16 or bfloat16 weights "
+                                               "(got %s)")
     if not t.is_contiguous() or t.numel() != R * NB * BL:
         raise ValueError("expected a contiguous tensor of %d x %d x %d elements" % (R, NB, BL))
     if out is not None and not (out.is_cuda and out.is_contiguous() and out.dtype == t.dtype and
@@ -71,7 +68,7 @@ def encode_qdq(t: torch.Tensor, R: int, NB: int, BL: int, bitwidth: int, symmetr
         factor = torch.empty(R, dtype=torch.float64, device=t.device)
     with torch.cuda.device(t.device):
         _native.call("aimet_bq_encode_qdq", t.data_ptr(), None if out is None else out.data_ptr(), R, NB, BL,
-                     _IO_CODES[t.dtype], int(bitwidth), int(bool(symmetric)), int(bool(strict)), int(bool(unsigned)),
+                     code, int(bitwidth), int(bool(symmetric)), int(bool(strict)), int(bool(unsigned)),
                      int(scale_bitwidth), table.data_ptr(), None if q is None else q.data_ptr(),
                      None if factor is None else factor.data_ptr(), torch.cuda.current_stream(t.device).cuda_stream)
     return table, q, factor
@@ -248,7 +245,7 @@ class BlockwiseQuantizer(StaticGridTensorQuantizer):
         if not tensor.is_cuda:
             raise RuntimeError("aimet_amd: blockwise quantization has no CPU path")
         dtype = tensor.dtype
-        t = tensor.detach() if dtype in _IO_CODES else tensor.detach().to(torch.float32)
+        t = tensor.detach() if dtype in _native.IO_CODES else tensor.detach().to(torch.float32)
         t = t.contiguous()
         if t.numel() != self.num_encodings * self.BL:
             raise ValueError("tensor of %d elements for %d blocks of %d" % (t.numel(), self.num_encodings, self.BL))

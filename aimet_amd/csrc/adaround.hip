@@ -22,6 +22,7 @@
 #include "common.hpp"
 #include "fast_pow.hpp"
 #include "recon.hpp"
+#include "reduce.hpp"
 #include "sleef_pow.hpp"
 #include "stream_map.hpp"   // aligned16
 
@@ -485,19 +486,14 @@ __global__ __launch_bounds__(kBlock) void adaround_fwd_kernel(const float* __res
     }
 }
 
+// +0 + the four wave sums in order; every thread but thread 0 gets +0. Starting from the identity
+// and starting from wave 0's own sum differ only when that sum is -0, which cannot occur: every
+// caller's value starts at +0.0f and only adds terms, and a round-to-nearest sum that starts from +0
+// is never -0.
 __device__ __forceinline__ float block_sum(float v)
 {
     __shared__ float s[kBlock / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0)
-        s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = 0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < kBlock / 64; ++i)
-            r += s[i];
+    const float r = block_fold_from<kBlock / 64>(0.0f, v, s, [](float a, float b) { return a + b; });
     __syncthreads();
     return r;
 }

@@ -37,6 +37,8 @@
 // (probs == scores) is safe on both paths: a row is read completely before any of it is written.
 
 #include "common.hpp"
+#include "io16.hpp"
+#include "reduce.hpp"
 #include "rnn_math.hpp"
 
 namespace aimet_amd
@@ -120,23 +122,15 @@ __device__ __forceinline__ float prob_of(const Args& a, float e, float s, float 
     return a.prob_qdq ? dequantize(quantize_nearest_rcp(p, a.pp, p_rcp), a.pp) : p;
 }
 
+// `o > v ? o : v`: a NaN in another lane is never taken
 __device__ __forceinline__ float wave_max(float v)
 {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-    {
-        const float o = __shfl_xor(v, d, kWave);
-        v             = o > v ? o : v;
-    }
-    return v;
+    return wave_all(v, [](float v, float o) { return o > v ? o : v; });
 }
 
 __device__ __forceinline__ float wave_sum(float v)
 {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        v = v + __shfl_xor(v, d, kWave);
-    return v;
+    return wave_all(v, [](float v, float o) { return v + o; });
 }
 
 // ---- wave path: NI values a lane ---------------------------------------------------------------
@@ -180,13 +174,6 @@ __global__ __launch_bounds__(kBlk) void attn_softmax_wave(const Args a)
 }
 
 // ---- LDS path ----------------------------------------------------------------------------------
-// floats before the first 16-byte boundary at or after p (p is 4-byte aligned), at most n
-__device__ __forceinline__ int head_of(const void* p, int n)
-{
-    const int h = (int) ((16u - (unsigned) (reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) >> 2;
-    return h < n ? h : n;
-}
-
 __global__ __launch_bounds__(kBlk) void attn_softmax_lds(const Args a)
 {
     extern __shared__ float4 lds4[];

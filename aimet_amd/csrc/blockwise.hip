@@ -37,6 +37,7 @@
 #include "common.hpp"
 #include "io16.hpp"
 #include "mse_core.hpp"
+#include "reduce.hpp"
 
 namespace aimet_amd
 {
@@ -54,39 +55,6 @@ constexpr unsigned kMaxGrid = 1u << 16;
 static_assert(kMaxBlocks * kMetaBytes + 64 < kLdsBytes, "a row's block table must fit LDS");
 
 LaunchCounter g_launches;
-
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
-template <int IO>
-struct Io
-{
-    using T   = unsigned short;
-    using Vec = u16x8;
-    static constexpr int V = 8;
-    static __device__ __forceinline__ float up(T x)
-    {
-        return to_f32<IO>(x);
-    }
-    static __device__ __forceinline__ T down(float f)
-    {
-        return from_f32<IO>(f);
-    }
-};
-template <>
-struct Io<IO_F32>
-{
-    using T   = float;
-    using Vec = f4;
-    static constexpr int V = 4;
-    static __device__ __forceinline__ float up(float x)
-    {
-        return x;
-    }
-    static __device__ __forceinline__ float down(float f)
-    {
-        return f;
-    }
-};
 
 struct Args
 {
@@ -133,24 +101,11 @@ struct MinMax
     // every lane of an aligned group of `seg` lanes ends with the group's min / max
     __device__ __forceinline__ void fold(int seg)
     {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1)
-            if (d < seg)
-            {
-                const float a = __shfl_xor(mn, d, kWave), b = __shfl_xor(mx, d, kWave);
-                mn            = a < mn ? a : mn;
-                mx            = b > mx ? b : mx;
-            }
+        *this = wave_all(*this, [](const MinMax& m, const MinMax& o) {
+            return MinMax {o.mn < m.mn ? o.mn : m.mn, o.mx > m.mx ? o.mx : m.mx};
+        }, seg);
     }
 };
-
-// elements before the first 16-byte boundary at or after p, at most n
-template <class T>
-__device__ __forceinline__ int head_of(const T* p, int n)
-{
-    const int h = (int) (((16u - (unsigned) (reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) / sizeof(T));
-    return h < n ? h : n;
-}
 
 __device__ __forceinline__ void wave_sync()
 {
@@ -160,26 +115,26 @@ __device__ __forceinline__ void wave_sync()
 }
 
 template <int IO>
-__device__ __forceinline__ typename Io<IO>::T qdq_elem(typename Io<IO>::T x, const QdqParams& p)
+__device__ __forceinline__ typename Io<IO>::elem_t qdq_elem(typename Io<IO>::elem_t x, const QdqParams& p)
 {
-    return Io<IO>::down(dequantize(quantize_nearest(Io<IO>::up(x), p), p));
+    return Io<IO>::store(dequantize(quantize_nearest(Io<IO>::load(x), p), p));
 }
 
 template <int IO>
-__device__ __forceinline__ typename Io<IO>::Vec qdq_vec(typename Io<IO>::Vec v, const QdqParams& p)
+__device__ __forceinline__ typename Io<IO>::vec_t qdq_vec(typename Io<IO>::vec_t v, const QdqParams& p)
 {
 #pragma unroll
-    for (int k = 0; k < Io<IO>::V; ++k)
+    for (int k = 0; k < Io<IO>::width; ++k)
         v[k] = qdq_elem<IO>(v[k], p);
     return v;
 }
 
 template <int IO>
-__device__ __forceinline__ void take_vec(MinMax& m, typename Io<IO>::Vec v)
+__device__ __forceinline__ void take_vec(MinMax& m, typename Io<IO>::vec_t v)
 {
 #pragma unroll
-    for (int k = 0; k < Io<IO>::V; ++k)
-        m.take(Io<IO>::up(v[k]));
+    for (int k = 0; k < Io<IO>::width; ++k)
+        m.take(Io<IO>::load(v[k]));
 }
 
 __device__ __forceinline__ QdqParams params_of(const float4& c)
@@ -222,12 +177,7 @@ __device__ __forceinline__ void encode_row(const Args& a, const Meta& m, double*
     }
     if (!lpbq)
         return;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-    {
-        const double o = __shfl_xor(dmax, d, kWave);
-        dmax           = o > dmax ? o : dmax;
-    }
+    dmax = wave_all(dmax, [](double m, double o) { return o > m ? o : m; });
     if constexpr (GROUP)
     {
         if ((tid & (kWave - 1)) == 0)
@@ -256,9 +206,9 @@ template <int IO, int NV>
 __global__ __launch_bounds__(kBlk) void bq_wave(const Args a)
 {
     using X   = Io<IO>;
-    using T   = typename X::T;
-    using Vec = typename X::Vec;
-    constexpr int V = X::V;
+    using T   = typename X::elem_t;
+    using Vec = typename X::vec_t;
+    constexpr int V = X::width;
     extern __shared__ float4 lds4[];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const Meta m   = meta_at(reinterpret_cast<char*>(lds4) + (size_t) wave * a.NB * kMetaBytes, a.NB);
@@ -286,12 +236,12 @@ __global__ __launch_bounds__(kBlk) void bq_wave(const Args a)
                 if (s < head)
                 {
                     hs[k] = bp[s];
-                    mm.take(X::up(hs[k]));
+                    mm.take(X::load(hs[k]));
                 }
                 if (s < BL - tail)
                 {
                     ts[k] = bp[tail + s];
-                    mm.take(X::up(ts[k]));
+                    mm.take(X::load(ts[k]));
                 }
             }
             const int vi = p * SEG + s;
@@ -349,9 +299,9 @@ template <int IO, bool RESIDENT>
 __global__ __launch_bounds__(kBlk) void bq_group(const Args a)
 {
     using X   = Io<IO>;
-    using T   = typename X::T;
-    using Vec = typename X::Vec;
-    constexpr int V = X::V;
+    using T   = typename X::elem_t;
+    using Vec = typename X::vec_t;
+    constexpr int V = X::width;
     extern __shared__ float4 lds4[];
     const Meta m = meta_at(lds4, a.NB);
     double* red  = reinterpret_cast<double*>(reinterpret_cast<char*>(lds4) + (size_t) a.NB * kMetaBytes);   // 4
@@ -380,7 +330,7 @@ __global__ __launch_bounds__(kBlk) void bq_group(const Args a)
                     const T x = bp[i];
                     if constexpr (RESIDENT)
                         row[base + i] = x;
-                    mm.take(X::up(x));
+                    mm.take(X::load(x));
                 }
                 for (int vi = s; vi < nvec; vi += SEG)
                 {
@@ -399,7 +349,7 @@ __global__ __launch_bounds__(kBlk) void bq_group(const Args a)
                     const T x = bp[i];
                     if constexpr (RESIDENT)
                         row[base + i] = x;
-                    mm.take(X::up(x));
+                    mm.take(X::load(x));
                 }
             }
             mm.fold(SEG);

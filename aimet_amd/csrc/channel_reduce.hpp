@@ -26,6 +26,7 @@
 #include <string>
 
 #include "common.hpp"
+#include "reduce.hpp"
 
 namespace aimet_amd
 {
@@ -35,21 +36,10 @@ constexpr int64_t kPieceFloats = 4096;   // planar: floats of one segment a work
 constexpr int64_t kMinPerGroup = 8192;   // elements below which a further split is not worth a workgroup
 constexpr int64_t kVecInner    = 128;    // planar segments shorter than this are read flat, 4 bytes a lane
 
-// Fixed-shape tree over the workgroup's 256 partials; lane 0's return value is the sum.
+static_assert(kReduceBlock == kTreeBlock, "block_sum is reduce.hpp's 256-lane tree");
 __device__ __forceinline__ double block_sum(double v, double* lds)
 {
-    const int t = threadIdx.x;
-    lds[t]      = v;
-    __syncthreads();
-    for (int s = kReduceBlock / 2; s > 0; s >>= 1)
-    {
-        if (t < s)
-            lds[t] = lds[t] + lds[t + s];
-        __syncthreads();
-    }
-    const double r = lds[0];
-    __syncthreads();
-    return r;
+    return block_tree(v, lds, [](double a, double b) { return a + b; });
 }
 
 // ---- accumulators --------------------------------------------------------------------------------

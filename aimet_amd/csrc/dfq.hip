@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "reduce.hpp"
 
 namespace aimet_amd
 {
@@ -20,6 +21,7 @@ namespace
 {
 
 constexpr int kDfqBlock = 256;
+static_assert(kDfqBlock == kTreeBlock, "the spans go through reduce.hpp's 256-lane tree");
 
 LaunchCounter g_launches;
 
@@ -103,29 +105,11 @@ __device__ __forceinline__ void span_apply(const Span& sp, F&& f)
     }
 }
 
-// Fixed-shape tree over the workgroup's 256 partials; every lane gets the result.
-template <class Op>
-__device__ __forceinline__ float block_reduce(float v, float* lds, Op op)
-{
-    const int t = threadIdx.x;
-    lds[t]      = v;
-    __syncthreads();
-    for (int s = kDfqBlock / 2; s > 0; s >>= 1)
-    {
-        if (t < s)
-            lds[t] = op(lds[t], lds[t + s]);
-        __syncthreads();
-    }
-    const float r = lds[0];
-    __syncthreads();
-    return r;
-}
-
 __device__ __forceinline__ float span_absmax(const Span& sp, float* lds)
 {
     float m = 0.0f;
     span_apply<false>(sp, [&](float& x) { m = nan_max(m, __builtin_fabsf(x)); });
-    return block_reduce(m, lds, [](float a, float b) { return nan_max(a, b); });
+    return block_tree(m, lds, [](float a, float b) { return nan_max(a, b); });
 }
 
 __device__ __forceinline__ void span_scale(const Span& sp, float s)
@@ -277,8 +261,8 @@ __global__ __launch_bounds__(kDfqBlock) void dfq_bn_fold_kernel(const BnJob* job
     if (bad)
         status[blockIdx.y] = 1;
     auto add      = [](float x, float y) { return x + y; };
-    sum_beta      = block_reduce(sum_beta, lds, add);
-    sum_mu        = block_reduce(sum_mu, lds, add);
+    sum_beta      = block_tree(sum_beta, lds, add);
+    sum_mu        = block_tree(sum_mu, lds, add);
     if (threadIdx.x == 0)
         j.bias[o] = (sum_beta - sum_mu) + j.bias[o];
 }
@@ -327,7 +311,7 @@ __global__ __launch_bounds__(kDfqBlock) void dfq_bias_fold_kernel(const float* g
             w2d = w2d + seg[q];
         acc = acc + w2d * hbf_absorb(gamma, beta, scale, relu, c);
     }
-    acc = block_reduce(acc, lds, [](float x, float y) { return x + y; });
+    acc = block_tree(acc, lds, [](float x, float y) { return x + y; });
     if (threadIdx.x == 0)
         bias2[o] = bias2[o] + acc;
 }

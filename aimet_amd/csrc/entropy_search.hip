@@ -39,6 +39,7 @@
 // host's winner too.
 #include "entropy_kl.hpp"
 #include "mse_core.hpp"
+#include "reduce.hpp"
 #include "tq_state.hpp"
 
 namespace aimet_amd
@@ -630,17 +631,18 @@ __global__ __launch_bounds__(kEntBlock) __attribute__((amdgpu_waves_per_eu(5))) 
         // U = min (kl + err) >= the smallest divergence; a window with kl - err > U + T, T above
         // the near-tie tolerance 1e-11 (mag_k + mag_best) + 1e-14, is larger than the minimum by
         // more than that tolerance: it is neither the winner nor a near-tie, and is not evaluated
-        double up = t < nv ? est.kl + est.err : __builtin_inf();
-        double mg = t < nv ? est.mag : 0.0;
-        for (int o = 32; o > 0; o >>= 1)
+        struct Bound
         {
-            up = __builtin_fmin(up, __shfl_xor(up, o, 64));
-            mg = __builtin_fmax(mg, __shfl_xor(mg, o, 64));
-        }
+            double up, mg;
+        };
+        const Bound bound = wave_all(Bound {t < nv ? est.kl + est.err : __builtin_inf(), t < nv ? est.mag : 0.0},
+                                   [](const Bound& a, const Bound& b) {
+                                       return Bound {__builtin_fmin(a.up, b.up), __builtin_fmax(a.mg, b.mg)};
+                                   });
         if (lane == 0)
         {
-            s_best_v[wave] = up;
-            s_mag[wave]    = mg;
+            s_best_v[wave] = bound.up;
+            s_mag[wave]    = bound.mg;
         }
         __syncthreads();
         double U = __builtin_inf(), maxmag = 0.0;
@@ -697,22 +699,18 @@ __global__ __launch_bounds__(kEntBlock) __attribute__((amdgpu_waves_per_eu(5))) 
             m = s_mt[t];
         }
         // (value, index) argmin: the smallest value below +inf, the first index among equals
-        double bv = (t < nv && v < __builtin_inf()) ? v : __builtin_inf();
-        int bk    = bv < __builtin_inf() ? t : kEntBlock;
-        for (int o = 32; o > 0; o >>= 1)
+        struct First
         {
-            const double ov = __shfl_xor(bv, o, 64);
-            const int ok    = __shfl_xor(bk, o, 64);
-            if (ov < bv || (ov == bv && ok < bk))
-            {
-                bv = ov;
-                bk = ok;
-            }
-        }
+            double v;
+            int k, pad;   // pad: the record is four whole words, each with a value
+        };
+        const double bv0 = (t < nv && v < __builtin_inf()) ? v : __builtin_inf();
+        const First first = wave_best(First {bv0, bv0 < __builtin_inf() ? t : kEntBlock, 0},
+                                     [](const First& o, const First& b) { return o.v < b.v || (o.v == b.v && o.k < b.k); });
         if (lane == 0)
         {
-            s_best_v[wave] = bv;
-            s_best_k[wave] = bk;
+            s_best_v[wave] = first.v;
+            s_best_k[wave] = first.k;
         }
         if (t == 0)
             s_tie = 0;

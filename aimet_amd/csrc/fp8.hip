@@ -31,6 +31,7 @@
 //     alone, results repeat bit for bit. The candidate maxima are torch.linspace's float32 values,
 //     built on the device from max|x|.
 #include "common.hpp"
+#include "reduce.hpp"
 #include "stream_map.hpp"
 
 #include <atomic>
@@ -209,23 +210,6 @@ void check_search_shape(int64_t outer, int64_t C, int64_t K)
     AIMET_REQUIRE(p.rows * p.S < (int64_t(1) << 31), "range search: too many workgroups");
 }
 
-__device__ __forceinline__ float wave_max_all(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v = __builtin_fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-// every lane gets the same sum: each butterfly step adds the same two values on both sides
-__device__ __forceinline__ float wave_sum_all(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // workgroup b -> row (o, c) and its run of tiles [e0, e1) of the row's K elements
 struct SearchBlock
 {
@@ -252,7 +236,7 @@ __global__ __launch_bounds__(64) void fp8_absmax_part_kernel(const float* __rest
     float m          = 0.0f;
     for (int64_t e = b.e0 + threadIdx.x; e < b.e1; e += 64)
         m = __builtin_fmaxf(m, __builtin_fabsf(row[e]));
-    m = wave_max_all(m);
+    m = wave_all(m, [](float a, float b) { return __builtin_fmaxf(a, b); });   // drops a NaN
     if (threadIdx.x == 0)
         part[b.c * P + b.o * S + b.s] = m;
 }
@@ -266,17 +250,9 @@ __global__ __launch_bounds__(kBlock) void fp8_absmax_fold_kernel(const float* __
     float m = 0.0f;
     for (int64_t p = threadIdx.x; p < P; p += kBlock)
         m = __builtin_fmaxf(m, part[c * P + p]);
-    m = wave_max_all(m);
-    if ((threadIdx.x & 63) == 0)
-        s_m[threadIdx.x >> 6] = m;
-    __syncthreads();
+    m = block_fold_own<kBlock / 64>(m, s_m, [](float a, float b) { return __builtin_fmaxf(a, b); });
     if (threadIdx.x == 0)
-    {
-#pragma unroll
-        for (int w = 1; w < kBlock / 64; ++w)
-            m = __builtin_fmaxf(m, s_m[w]);
         absmax[c] = m;
-    }
 }
 
 // candidate i of a channel whose max|x| is mx: torch.linspace(0.1 * mx.item(), 1.2 * mx.item(), 111)
@@ -350,7 +326,8 @@ __global__ __launch_bounds__(64) void fp8_search_part_kernel(const float* __rest
                     }
                 }
             const float acc = (a4[0] + a4[1]) + (a4[2] + a4[3]);
-            const float s = wave_sum_all(acc);
+            // every lane gets the same sum: each butterfly step adds the same two values on both sides
+            const float s = wave_all(acc, [](float a, float b) { return a + b; });
             if (lane == (i & 63))
             {
                 if (i < 64)
@@ -420,26 +397,19 @@ __global__ __launch_bounds__(kFoldGroups* kFoldLanes) void fp8_search_fold_kerne
         v[h] = i < kCand ? s : inf;
     }
     // argmin as torch's: the first index of the least value; a NaN loss is the least of all
-    float bv = v[0];
-    int bi   = lane;
-    if (v[1] != v[1] ? bv == bv : v[1] < bv)
+    struct Best
     {
-        bv = v[1];
-        bi = 64 + lane;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-    {
-        const float ov = __shfl_xor(bv, off, 64);
-        const int oi   = __shfl_xor(bi, off, 64);
-        const bool bn = bv != bv, on = ov != ov;
-        const bool take = (on && !bn) || (on == bn && (ov < bv || ((ov == bv || on) && oi < bi)));
-        if (take)
-        {
-            bv = ov;
-            bi = oi;
-        }
-    }
+        float v;
+        int i;
+    };
+    const auto better = [](const Best& o, const Best& b) {
+        const bool bn = b.v != b.v, on = o.v != o.v;
+        return (on && !bn) || (on == bn && (o.v < b.v || ((o.v == b.v || on) && o.i < b.i)));
+    };
+    Best b {v[0], lane};
+    if (v[1] != v[1] ? b.v == b.v : v[1] < b.v)
+        b = Best {v[1], 64 + lane};
+    const int bi = wave_best(b, better).i;
     if (lane == 0)
     {
         best[c] = fp8_candidate(absmax[c], bi);

@@ -376,6 +376,8 @@ __global__ __launch_bounds__(kRowsPerWg * 64) void update_wave_kernel(UpdateArgs
                     idx  = k;
                 }
             }
+        // (kept local: on reduce.hpp's wave_best update_wave_kernel<0, true> spills SGPRs into VGPR lanes,
+        // profiles/r25/reduce_isa.txt)
         // the wave's first minimum: butterfly on (distance, index)
 #pragma unroll
         for (int m = 32; m > 0; m >>= 1)

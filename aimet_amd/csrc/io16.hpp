@@ -7,6 +7,8 @@
 
 #include <cstdint>
 
+#include "vec_types.hpp"
+
 namespace aimet_amd
 {
 
@@ -49,5 +51,64 @@ __device__ __forceinline__ unsigned short from_f32(float f)
     }
 }
 
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+
+// One I/O dtype as a kernel sees it: element type, 16-byte vector type and its width, and the
+// roundings. The values match aimet_amd/_native.py's IO_CODES.
+template <int IO>
+struct Io
+{
+    using elem_t = unsigned short;
+    using vec_t  = u16x8;
+    static constexpr int width = 8;
+    static __device__ __forceinline__ float load(elem_t e)
+    {
+        return to_f32<IO>(e);
+    }
+    static __device__ __forceinline__ elem_t store(float f)
+    {
+        return from_f32<IO>(f);
+    }
+    // f is not NaN (from_f32's MAYBE_NAN)
+    static __device__ __forceinline__ elem_t store_number(float f)
+    {
+        return from_f32<IO, false>(f);
+    }
+    static __device__ __forceinline__ float round(float f)   // [f]_T
+    {
+        return to_f32<IO>(from_f32<IO>(f));
+    }
+};
+template <>
+struct Io<IO_F32>
+{
+    using elem_t = float;
+    using vec_t  = f4;
+    static constexpr int width = 4;
+    static __device__ __forceinline__ float load(float e)
+    {
+        return e;
+    }
+    static __device__ __forceinline__ float store(float f)
+    {
+        return f;
+    }
+    static __device__ __forceinline__ float store_number(float f)
+    {
+        return f;
+    }
+    static __device__ __forceinline__ float round(float f)
+    {
+        return f;
+    }
+};
+
+// elements before the first 16-byte boundary at or after p (aligned to its element), at most n
+template <class T>
+__device__ __forceinline__ int head_of(const T* p, int n)
+{
+    const int h = (int) (((16u - (unsigned) (reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) / sizeof(T));
+    return h < n ? h : n;
+}
 
 }   // namespace aimet_amd

@@ -135,7 +135,6 @@ __device__ __forceinline__ void lg_qdq_n(const float* x, float d, float o, float
 }
 
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
 // torch's maximum / minimum: a NaN operand is returned
 __device__ __forceinline__ float t_maximum(float a, float b)
@@ -415,6 +414,9 @@ __device__ __forceinline__ void lg_bwd_elems_fast(const float* x, const float* g
         lg_bwd_term_m<MODE>(x[k], lg_quot(x[k], dl, rcp), g[k], o, steps, gx[k], s);
 }
 
+// Kept local: on reduce.hpp's record form the 16-bit backward kernels vectorise their sums into packed
+// fp32 adds and multiplies and take 4 more VGPRs (profiles/r25/reduce_isa.txt). {+0, +0, +0} plus the
+// four wave triples in order; every thread but thread 0 gets zeros.
 __device__ __forceinline__ Sums block_reduce(Sums s)
 {
     __shared__ float sh[3][kBlock / 64];
@@ -559,15 +561,13 @@ __device__ __forceinline__ int64_t lg_tile_elem(int64_t base, int u, int k)
 // -- is one streamed 16-B vector of 16-bit values, or two of floats, held as loaded (regs_t) until
 // unpack() makes them 8 floats (the upcast is exact); store() converts 8 floats back (torch's
 // rounding, io16.hpp) and streams them out. store() forms its address after the conversion: handed
-// the address, the 16-bit kernels came out two VGPRs larger. up / down: one element, for the
-// element path.
+// the address, the 16-bit kernels came out two VGPRs larger. One element, for the element path, goes
+// through io16.hpp's Io<IO>.
 template <int IO>
 struct LgIo
 {
     typedef unsigned short elem_t;
     typedef u16x8 regs_t;
-    static __device__ __forceinline__ float up(elem_t v) { return to_f32<IO>(v); }
-    static __device__ __forceinline__ elem_t down(float v) { return from_f32<IO>(v); }
     static __device__ __forceinline__ regs_t load(const elem_t* p, int64_t base, int u)
     {
         return load_stream(reinterpret_cast<const u16x8*>(p) + lg_tile_elem(base, u, 0) / 8);
@@ -595,8 +595,6 @@ struct LgIo<IO_F32>
     {
         f4 lo, hi;
     };
-    static __device__ __forceinline__ float up(float v) { return v; }
-    static __device__ __forceinline__ float down(float v) { return v; }
     static __device__ __forceinline__ regs_t load(const float* p, int64_t base, int u)
     {
         const int64_t q = lg_tile_elem(base, u, 0) / 4;
@@ -672,9 +670,9 @@ __device__ __forceinline__ void lg_bwd_elem_tile(const typename LgIo<IO>::elem_t
             if (e >= n)
                 break;
             float r;
-            lg_bwd_elem(LgIo<IO>::up(x[e]), LgIo<IO>::up(g[e]), dl, o, steps, rcp, r, s, MODE);
+            lg_bwd_elem(Io<IO>::load(x[e]), Io<IO>::load(g[e]), dl, o, steps, rcp, r, s, MODE);
             if (gx)
-                gx[e] = LgIo<IO>::down(r);
+                gx[e] = Io<IO>::store(r);
         }
 }
 

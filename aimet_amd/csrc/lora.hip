@@ -55,60 +55,9 @@ QdqParams tensor_params(const aimet_tf_encoding& enc);   // qdq.hip
 namespace
 {
 
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kLoraLanes = 256;   // fixed: aimet_qdq_tile_lanes does not apply
 
 LaunchCounter g_launches;
-
-// element type, vector type and the roundings of one I/O dtype
-template <int IO>
-struct Io
-{
-    using elem_t = unsigned short;
-    using vec_t  = u16x8;
-    static constexpr int width = 8;
-    static __device__ __forceinline__ float load(elem_t e)
-    {
-        return to_f32<IO>(e);
-    }
-    static __device__ __forceinline__ elem_t store(float f)
-    {
-        return from_f32<IO>(f);
-    }
-    static __device__ __forceinline__ float round(float f)   // [f]_T
-    {
-        return to_f32<IO>(from_f32<IO>(f));
-    }
-    // f is not NaN (io16.hpp: from_f32's MAYBE_NAN)
-    static __device__ __forceinline__ elem_t store_number(float f)
-    {
-        return from_f32<IO, false>(f);
-    }
-};
-template <>
-struct Io<IO_F32>
-{
-    using elem_t = float;
-    using vec_t  = f4;
-    static constexpr int width = 4;
-    static __device__ __forceinline__ float load(float e)
-    {
-        return e;
-    }
-    static __device__ __forceinline__ float store(float f)
-    {
-        return f;
-    }
-    static __device__ __forceinline__ float round(float f)
-    {
-        return f;
-    }
-    static __device__ __forceinline__ float store_number(float f)
-    {
-        return f;
-    }
-};
 
 // one quantizer as the kernels see it (kernel arguments: SGPRs)
 struct Quant

@@ -8,6 +8,7 @@
 // candidate per lane, and keeps the first minimum; a second launch folds the slices in candidate
 // order. Arithmetic: mse_core.hpp, shared with the host path (bit-exact).
 #include "mse_core.hpp"
+#include "reduce.hpp"
 #include "tq_state.hpp"
 
 namespace aimet_amd
@@ -345,9 +346,7 @@ __device__ void search_slice(const TqDevice& d, int64_t c, int y, int splits, in
                 }
             }
             // the workgroup's best error so far (every lane's selected error is a complete one)
-            float m = bt >= 0 ? be : FLT_MAX;
-            for (int k = 32; k > 0; k >>= 1)
-                m = fminf(m, __shfl_xor(m, k, 64));
+            const float m = wave_all(bt >= 0 ? be : FLT_MAX, [](float a, float b) { return fminf(a, b); });
             if (lane == 0)
                 wmin[threadIdx.x >> 6] = m;
             __syncthreads();
@@ -356,19 +355,15 @@ __device__ void search_slice(const TqDevice& d, int64_t c, int y, int splits, in
                     wg_best = fminf(wg_best, wmin[w]);
             __syncthreads();
         }
-        for (int k = 32; k > 0; k >>= 1)
         {
-            float oe       = __shfl_xor(be, k, 64);
-            long long ot   = __shfl_xor(bt, k, 64);
-            float olo      = __shfl_xor(blo, k, 64);
-            float ohi      = __shfl_xor(bhi, k, 64);
-            if (better(oe, ot, be, bt))
+            struct Rec
             {
-                be  = oe;
-                bt  = ot;
-                blo = olo;
-                bhi = ohi;
-            }
+                long long t;
+                float e, lo, hi;
+            };
+            const Rec w = wave_best(Rec {bt, be, blo, bhi},
+                                    [](const Rec& o, const Rec& b) { return better(o.e, o.t, b.e, b.t); });
+            be = w.e, bt = w.t, blo = w.lo, bhi = w.hi;
         }
         if (lane == 0)
         {

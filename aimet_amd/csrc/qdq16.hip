@@ -21,8 +21,6 @@ namespace aimet_amd
 namespace
 {
 
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kLanes16 = 256;   // fixed: aimet_qdq_tile_lanes does not apply
 
 // thr = qdq_round_thr(p, rcp) (common.hpp), hoisted by the callers out of their element loops
@@ -65,13 +63,13 @@ struct Qdq16
         {
 #pragma unroll
             for (int k = 0; k < 8; ++k)
-                r[k] = from_f32<IO, false>(qdq<STOCHASTIC>(to_f32<IO>(v[k]), p, seed, e + k, rcp, thr));
+                r[k] = Io<IO>::store_number(qdq<STOCHASTIC>(Io<IO>::load(v[k]), p, seed, e + k, rcp, thr));
         }
         else
         {
 #pragma unroll
             for (int k = 0; k < 8; ++k)
-                r[k] = from_f32<IO>(qdq<STOCHASTIC>(to_f32<IO>(v[k]), p, seed, e + k, rcp, thr));
+                r[k] = Io<IO>::store(qdq<STOCHASTIC>(Io<IO>::load(v[k]), p, seed, e + k, rcp, thr));
         }
         store_stream(r, reinterpret_cast<u16x8*>(out) + i);
     }
@@ -81,15 +79,15 @@ struct Qdq16
         if constexpr (CH)
             q = load_params(table, (uint32_t) C, (uint32_t) ((i / K) % C));
         const float rcp = 1.0f / q.delta;
-        out[i] = from_f32<IO>(qdq<STOCHASTIC>(to_f32<IO>(in[i]), q, seed, (uint64_t) i, rcp, qdq_round_thr(q, rcp)));
+        out[i] = Io<IO>::store(qdq<STOCHASTIC>(Io<IO>::load(in[i]), q, seed, (uint64_t) i, rcp, qdq_round_thr(q, rcp)));
     }
 };
 
 template <int IO>
 __device__ __forceinline__ unsigned short ste16(unsigned short x, unsigned short g, float mn, float mx)
 {
-    const float xf = to_f32<IO>(x);
-    return from_f32<IO>(to_f32<IO>(g) * ((mn <= xf && xf <= mx) ? 1.0f : 0.0f));
+    const float xf = Io<IO>::load(x);
+    return Io<IO>::store(Io<IO>::load(g) * ((mn <= xf && xf <= mx) ? 1.0f : 0.0f));
 }
 
 template <int IO, bool CH>

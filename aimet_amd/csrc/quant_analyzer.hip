@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "io16.hpp"
+#include "reduce.hpp"
 
 namespace aimet_amd
 {
@@ -36,42 +37,18 @@ constexpr int64_t kQaMaxElems   = int64_t(1) << 40;
 LaunchCounter g_launches;       // aimet_qa_sq_err
 LaunchCounter g_amp_launches;   // aimet_amp_sqnr_add
 
-// Fixed-shape tree over the workgroup's 256 pairs; every lane returns with lds[0], lds[kQaBlock] the sums.
+static_assert(kQaBlock == kTreeBlock, "the pairs go through reduce.hpp's 256-lane tree");
+
+// every lane returns with lds[0], lds[kQaBlock] the sums
 __device__ __forceinline__ void block_sum2(double a, double b, double* lds)
 {
-    const int t       = threadIdx.x;
-    lds[t]            = a;
-    lds[kQaBlock + t] = b;
-    __syncthreads();
-    for (int s = kQaBlock / 2; s > 0; s >>= 1)
-    {
-        if (t < s)
-        {
-            lds[t]            = lds[t] + lds[t + s];
-            lds[kQaBlock + t] = lds[kQaBlock + t] + lds[kQaBlock + t + s];
-        }
-        __syncthreads();
-    }
+    block_tree2(a, b, lds, lds + kQaBlock, [](double x, double y) { return x + y; });
 }
 
 template <int IO>
-struct Elem
+__device__ __forceinline__ double widen(typename Io<IO>::elem_t v)
 {
-    using type = unsigned short;
-};
-template <>
-struct Elem<IO_F32>
-{
-    using type = float;
-};
-
-template <int IO>
-__device__ __forceinline__ double widen(typename Elem<IO>::type v)
-{
-    if constexpr (IO == IO_F32)
-        return (double) v;
-    else
-        return (double) to_f32<IO>(v);
+    return (double) Io<IO>::load(v);
 }
 
 // one element: d += (r - x)^2, q += r^2, one rounding per accumulation
@@ -104,11 +81,11 @@ __device__ __forceinline__ void add_vec(const uint4 r, const uint4 x, double (&d
 // rest (fewer than a vector). Workgroup b takes vectors b * 256 + t, then strides by the grid;
 // workgroup 0 also takes head and tail.
 template <int IO>
-__global__ __launch_bounds__(kQaBlock) void qa_sq_err_vec_kernel(const typename Elem<IO>::type* __restrict__ ref,
-                                                                 const typename Elem<IO>::type* __restrict__ x, int64_t n,
+__global__ __launch_bounds__(kQaBlock) void qa_sq_err_vec_kernel(const typename Io<IO>::elem_t* __restrict__ ref,
+                                                                 const typename Io<IO>::elem_t* __restrict__ x, int64_t n,
                                                                  int64_t head, int64_t nv, double* __restrict__ part)
 {
-    constexpr int EPV = 16 / (int) sizeof(typename Elem<IO>::type);
+    constexpr int EPV = 16 / (int) sizeof(typename Io<IO>::elem_t);
     __shared__ double lds[2 * kQaBlock];
     const int t = threadIdx.x;
     double d[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
@@ -136,8 +113,8 @@ __global__ __launch_bounds__(kQaBlock) void qa_sq_err_vec_kernel(const typename 
 
 // differently misaligned bases: element loads on both
 template <int IO>
-__global__ __launch_bounds__(kQaBlock) void qa_sq_err_elem_kernel(const typename Elem<IO>::type* __restrict__ ref,
-                                                                  const typename Elem<IO>::type* __restrict__ x, int64_t n,
+__global__ __launch_bounds__(kQaBlock) void qa_sq_err_elem_kernel(const typename Io<IO>::elem_t* __restrict__ ref,
+                                                                  const typename Io<IO>::elem_t* __restrict__ x, int64_t n,
                                                                   double* __restrict__ part)
 {
     __shared__ double lds[2 * kQaBlock];
@@ -210,7 +187,7 @@ __global__ __launch_bounds__(kQaBlock) void amp_sqnr_fold_kernel(const double* _
 template <int IO>
 int64_t launch_partials(const void* ref_v, const void* x_v, int64_t n, Scratch<double>& part, hipStream_t s)
 {
-    using T           = typename Elem<IO>::type;
+    using T           = typename Io<IO>::elem_t;
     constexpr int EPV = 16 / (int) sizeof(T);
     const T* ref      = static_cast<const T*>(ref_v);
     const T* x        = static_cast<const T*>(x_v);

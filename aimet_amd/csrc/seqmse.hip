@@ -313,6 +313,8 @@ __global__ __launch_bounds__(kReconBlock) void recon_rows_kernel(const float* __
     }
 }
 
+// A __shfl_down tree, local to this file: only lane 0's result is used (for lane 0 it is the xor
+// butterfly's tree with operands commuted).
 __device__ __forceinline__ float wave_sum(float v)
 {
 #pragma unroll

@@ -20,6 +20,7 @@
 // The single-quantizer kernels and the batched ones over job tables (*_many) are two layers over
 // one set of device functions, each body written once (DESIGN.md §5 lists them).
 #include "entropy_core.hpp"
+#include "reduce.hpp"
 #include "tq_state.hpp"
 
 #include <algorithm>
@@ -37,53 +38,27 @@ constexpr int kWaves      = kBlock / 64;
 constexpr int kHistUnroll = 4;
 constexpr int kHistGrid   = 2048;   // 8 workgroups per CU: enough 16-B loads in flight for HBM
 
-__device__ __forceinline__ float wave_min(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v = fminf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
 {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o, 64);
-    return v;
+    return wave_all(v, [](uint32_t a, uint32_t b) { return a + b; });
 }
 
 // Block-wide min/max; result valid in thread 0. NaNs never enter (fminf/fmaxf drop them),
 // matching GetMin_cpu/GetMax_cpu (std::min/std::max skip NaN, math_functions.cpp:327-347).
 // The sign of a zero extremum is immaterial downstream (TfEncodingAnalyzer.cpp:87-88 and
 // InitializePdf produce identical results for +0 and -0).
+struct MinMaxPair
+{
+    float mn, mx;
+};
 __device__ __forceinline__ void block_minmax(float& mn, float& mx)
 {
-    __shared__ float smn[kWaves], smx[kWaves];
-    mn       = wave_min(mn);
-    mx       = wave_max(mx);
-    int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0)
-    {
-        smn[w] = mn;
-        smx[w] = mx;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-#pragma unroll
-        for (int i = 1; i < kWaves; ++i)
-        {
-            mn = fminf(mn, smn[i]);
-            mx = fmaxf(mx, smx[i]);
-        }
-    }
+    __shared__ MinMaxPair s[kWaves];
+    const MinMaxPair r = block_fold_own<kWaves>(MinMaxPair {mn, mx}, s, [](const MinMaxPair& a, const MinMaxPair& b) {
+        return MinMaxPair {fminf(a.mn, b.mn), fmaxf(a.mx, b.mx)};
+    });
+    mn = r.mn;
+    mx = r.mx;
 }
 
 __device__ __forceinline__ void accum4(const float4& v, float& mn, float& mx)

@@ -7,6 +7,7 @@
 // (each lane evaluates its candidate's cost over the 512 bins in the reference's order, the PDF
 // broadcast from LDS), then a first-minimum argmin across the workgroup. The arithmetic is the
 // shared header tfe_core.hpp, compiled for the host and the device from one source (bit-exact).
+#include "reduce.hpp"
 #include "tfe_core.hpp"
 
 #include <algorithm>
@@ -170,23 +171,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK == 128 ? 5 : (BLOCK == 64 ? 2 : 7)) vo
                 b = me;
         }
         // wave argmin, then across waves
-        for (int k = 32; k > 0; k >>= 1)
-        {
-            Best o;
-            o.cost   = __shfl_xor(b.cost, k, 64);
-            o.idx    = __shfl_xor(b.idx, k, 64);
-            o.delta  = __shfl_xor(b.delta, k, 64);
-            o.offset = __shfl_xor(b.offset, k, 64);
-            if (better(o, b))
-                b = o;
-        }
-        if (lane == 0)
-            wbest[threadIdx.x >> 6] = b;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (int w = 1; w < kW; ++w)
-                if (better(wbest[w], b))
-                    b = wbest[w];
+        b = block_fold_own<kW>(b, wbest, keep_better([](const Best& o, const Best& mine) { return better(o, mine); }));
         bool finish = splits == 1;
         if (!finish)
         {

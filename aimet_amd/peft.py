@@ -78,8 +78,6 @@ from aimet_amd.transformers import _encoding_c   # TfEncoding or (min, max, bw) 
 
 PEFT_QUANTIZABLE_TYPES = DEFAULT_QUANTIZABLE_TYPES + (Add, Multiply)
 
-_IO_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}   # io_dtype of aimet_lora_*
-
 
 # ---- the launches --------------------------------------------------------------------------------
 def lora_launch_count(reset: bool = False) -> int:
@@ -96,11 +94,11 @@ def _ref(enc):
 def _check(what, *tensors):
     t0 = tensors[0]
     for t in tensors:
-        if not (t.is_cuda and t.dtype in _IO_CODES and t.is_contiguous()):
+        if not (t.is_cuda and t.dtype in _native.IO_CODES and t.is_contiguous()):
             raise ValueError("%s: tensors must be contiguous float32 / float16 / bfloat16 tensors on the GPU" % what)
         if t.dtype != t0.dtype or t.numel() != t0.numel() or t.device != t0.device:
             raise ValueError("%s: tensors must share one dtype, size and device" % what)
-    return _IO_CODES[t0.dtype]
+    return _native.IO_CODES[t0.dtype]
 
 
 def _stream(t):
@@ -294,7 +292,7 @@ class LoraLayer(nn.Module):
 
     def _fused_children(self, x, index):
         """The five wrappers when the fused route applies to x and adapter `index`, else None."""
-        if not (self.fused and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in _IO_CODES and
+        if not (self.fused and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in _native.IO_CODES and
                 x.is_contiguous() and not torch.is_autocast_enabled()):
             return None
         five = (self.base_layer, self.lora_A[index], self.mul_scale, self.lora_B[index], self.add_lora_to_res)

@@ -49,7 +49,6 @@ from aimet_amd.seq_mse import get_ordered_list_of_modules
 
 _logger = logging.getLogger("aimet_amd.quant_analyzer")
 
-_IO_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}   # aimet_qa_sq_err's io_dtype
 LAUNCHES_PER_LAYER_BATCH = 2    # aimet_qa_sq_err: the partial sums and their fold
 
 _bokeh_state = {"checked": False, "available": False}
@@ -74,7 +73,7 @@ def add_sq_err(ref: torch.Tensor, x: torch.Tensor, scale: float, acc: torch.Tens
     """acc[0] += scale * sum (ref - x)^2, acc[1] += scale * sum ref^2 (aimet_qa_sq_err): ref and x
     contiguous device tensors of one shape and dtype (float32 / float16 / bfloat16), acc two float64
     on the same device."""
-    if ref.shape != x.shape or ref.dtype != x.dtype or ref.dtype not in _IO_DTYPES:
+    if ref.shape != x.shape or ref.dtype != x.dtype or ref.dtype not in _native.IO_CODES:
         raise ValueError("squared error: needs two float32 / float16 / bfloat16 tensors of one shape and dtype")
     if not (ref.is_cuda and x.is_cuda and acc.is_cuda) or not (ref.is_contiguous() and x.is_contiguous()):
         raise ValueError("squared error: needs contiguous device tensors; the MI355X core has no CPU path")
@@ -82,7 +81,7 @@ def add_sq_err(ref: torch.Tensor, x: torch.Tensor, scale: float, acc: torch.Tens
         raise ValueError("squared error: the accumulator is two contiguous float64")
     with torch.cuda.device(ref.device):
         _native.call("aimet_qa_sq_err", ctypes.c_void_p(ref.data_ptr()), ctypes.c_void_p(x.data_ptr()), ref.numel(),
-                     _IO_DTYPES[ref.dtype], float(scale), ctypes.c_void_p(acc.data_ptr()),
+                     _native.IO_CODES[ref.dtype], float(scale), ctypes.c_void_p(acc.data_ptr()),
                      ctypes.c_void_p(torch.cuda.current_stream(ref.device).cuda_stream))
 
 
@@ -525,7 +524,7 @@ class QuantAnalyzer:
                 if name in seen_ref or name in skipped:
                     return
                 seen_ref.add(name)
-                if not isinstance(out, torch.Tensor) or out.dtype not in _IO_DTYPES or out.dim() == 0:
+                if not isinstance(out, torch.Tensor) or out.dtype not in _native.IO_CODES or out.dim() == 0:
                     skip(name, "its output is not one float32 / float16 / bfloat16 tensor")
                     return
                 out = out.detach()
