@@ -287,6 +287,9 @@ _PROTOTYPES = {
     "aimet_bq_encode_qdq": [_vp, _vp, _i64, _i64, _i64, _int, _i32, _int, _int, _int, _int, _vp, _vp, _vp, _vp],
     "aimet_bq_row_path": [_i64, _i64, _int, ctypes.POINTER(_int)],
     "aimet_bq_launch_count": [_i64p, _int],
+    "aimet_lg_block_forward": [_vp, _vp, _i64, _i64, _int, _vp, _vp, _int, _int, _int, _int, _vp, _vp],
+    "aimet_lg_block_backward": [_vp, _vp, _int, _vp, _i64, _i64, _vp, ctypes.c_float, _int, _vp, _vp, _vp],
+    "aimet_lg_block_round": [_i64, _int, _i64p],
 }
 _RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p,
              "aimet_attn_softmax_max_s": ctypes.c_int64}

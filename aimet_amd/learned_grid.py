@@ -221,6 +221,90 @@ class LearnedGridQuantizeDequantize(torch.autograd.Function):
         return gx_out, gmin, gmax, None, None, None, None, None, None
 
 
+BLOCK_MAX_BL = 1024   # AIMET_LG_BLOCK_MAX_BL: longer blocks are per-channel rows of the [1, E, BL] view
+
+
+def block_round(block_len: int, out_dtype=torch.float32) -> int:
+    """The blocks one trip of the block kernels' grid covers (aimet_lg_block_round)."""
+    n = ctypes.c_int64(0)
+    _native.call("aimet_lg_block_round", int(block_len), _native.IO_CODES[out_dtype], ctypes.byref(n))
+    return n.value
+
+
+class LearnedGridBlockQuantizeDequantize(torch.autograd.Function):
+    """apply(tensor, encoding_min, encoding_max, block_len, bitwidth, use_symmetric, use_strict_symmetric,
+    is_unsigned_symmetric, out_dtype=None): LearnedGridQuantizeDequantize's contract over a weight
+    viewed as [E][block_len], block e with the range (encoding_min[e], encoding_max[e]) -- 1-D [E]
+    vectors in [channel][block] order. One launch forward (aimet_lg_block_forward: y, cast to
+    out_dtype in the store when that is fp16 / bf16, and the saved encoding) and one backward
+    (aimet_lg_block_backward: a 16-bit gradient upcast in the loads, grad_x skipped when not needed,
+    the range gradients folded in the kernel). A 16-bit or CPU weight is upcast / staged."""
+
+    @staticmethod
+    def forward(ctx, tensor, encoding_min, encoding_max, block_len, bitwidth, use_symmetric=False,
+                use_strict_symmetric=False, is_unsigned_symmetric=False, out_dtype=None):
+        if bitwidth >= 32:
+            raise RuntimeError("Invalid bitwidth: %d" % bitwidth)
+        E = encoding_min.numel()
+        if encoding_max.numel() != E or tensor.numel() != E * block_len:
+            raise ValueError("%d elements are not %d blocks of %d" % (tensor.numel(), E, block_len))
+        orig_dtype = tensor.dtype
+        x, staged = _stage(tensor.to(torch.float32), "tensor")
+        x = x.contiguous()
+        fused = out_dtype in IO_DTYPES and orig_dtype == torch.float32 and not staged
+        y = torch.empty(x.shape, dtype=out_dtype if fused else torch.float32, device=x.device)
+        emin = encoding_min.detach().to(x.device, torch.float32).reshape(-1).contiguous()
+        emax = encoding_max.detach().to(x.device, torch.float32).reshape(-1).contiguous()
+        enc = _saved_encoding(emin)
+        with torch.cuda.device(x.device):
+            _native.call("aimet_lg_block_forward", x.data_ptr(), y.data_ptr(), E, int(block_len),
+                         _native.IO_CODES[y.dtype], emin.data_ptr(), emax.data_ptr(), int(bitwidth),
+                         int(bool(use_symmetric)), int(bool(use_strict_symmetric)), int(bool(is_unsigned_symmetric)),
+                         enc.data_ptr(), _stream(x))
+        ctx.save_for_backward(x, enc)
+        mode = 2 if not use_symmetric else (1 if is_unsigned_symmetric else 0)
+        ctx.cfg = (E, int(block_len), num_steps_of(bitwidth, use_symmetric, use_strict_symmetric), mode, orig_dtype,
+                   encoding_min.shape, encoding_max.shape, staged)
+        if fused:
+            return y
+        return y.to(orig_dtype).cpu() if staged else y.to(orig_dtype)
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, enc = ctx.saved_tensors
+        E, block_len, steps, mode, dtype, min_shape, max_shape, staged = ctx.cfg
+        g = grad.to(x.device)
+        g = (g if g.dtype in _native.IO_CODES else g.to(torch.float32)).contiguous()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gmin = torch.empty(E, dtype=torch.float32, device=x.device)
+        gmax = torch.empty_like(gmin)
+        with torch.cuda.device(x.device):
+            _native.call("aimet_lg_block_backward", x.data_ptr(), g.data_ptr(), _native.IO_CODES[g.dtype],
+                         None if gx is None else gx.data_ptr(), E, block_len, enc.data_ptr(), steps, mode,
+                         gmin.data_ptr(), gmax.data_ptr(), _stream(x))
+        gx = gx.to(dtype) if gx is not None else None
+        gmin, gmax = gmin.view(min_shape), gmax.view(max_shape)
+        if staged:
+            gx = gx.cpu() if gx is not None else None
+            gmin, gmax = gmin.cpu(), gmax.cpu()
+        return gx, gmin, gmax, None, None, None, None, None, None
+
+
+def quantize_dequantize_blocks(tensor, encoding_min, encoding_max, block_len, bitwidth, use_symmetric=False,
+                               use_strict_symmetric=False, is_unsigned_symmetric=False, out_dtype=None):
+    """The learned-grid op over `tensor` viewed as [E][block_len]: the block kernels up to
+    BLOCK_MAX_BL elements a block, above it the per-channel op on the [1, E, block_len] view (its
+    kernels are built for long channels)."""
+    if block_len <= BLOCK_MAX_BL:
+        return LearnedGridBlockQuantizeDequantize.apply(tensor, encoding_min, encoding_max, block_len, bitwidth,
+                                                        use_symmetric, use_strict_symmetric, is_unsigned_symmetric,
+                                                        out_dtype)
+    y = LearnedGridQuantizeDequantize.apply(tensor.reshape(1, encoding_min.numel(), block_len), encoding_min,
+                                            encoding_max, bitwidth, use_symmetric, use_strict_symmetric,
+                                            is_unsigned_symmetric, 1, out_dtype)
+    return y.view(tensor.shape)
+
+
 def _gate_fusable(encoding_min, encoding_max):
     return (encoding_min.is_cuda and encoding_max.is_cuda and encoding_min.dtype == torch.float32
             and encoding_max.dtype == torch.float32 and encoding_min.is_contiguous() and encoding_max.is_contiguous()

@@ -895,7 +895,17 @@ def construct_learned_grid_wrapper(post_training_module: StaticGridQuantWrapper,
         list(zip(trainable.input_quantizers, post_training_module.input_quantizers)) + \
         [(trainable.param_quantizers[n], q) for n, q in post_training_module.param_quantizers.items()]
     for new, old in pairs:
-        initialize_learned_grid_quantizer_attributes(new, old)
+        if getattr(old, "learn_ranges", False):
+            # a blockwise quantizer with learned ranges: one trainable (min, max) per block, built on
+            # the device from the calibrated table (a Llama MLP weight has ~0.9 M blocks)
+            from aimet_amd.blockwise import LearnedBlockwiseQuantizer
+            learned = LearnedBlockwiseQuantizer(old)
+            learned.name, learned.wrapper_ref, learned.device, learned._ch_axis = new.name, trainable, device, 0
+            trainable.param_quantizers[new.name] = new = learned
+            if new.enabled and old.table is not None:
+                new.ranges_from_table(old, device)
+        else:
+            initialize_learned_grid_quantizer_attributes(new, old)
         if new.encoding_min_max_fixed_vals is not None:
             new.freeze_encoding()
     return trainable

@@ -1127,6 +1127,35 @@ int aimet_bq_row_path(int64_t NB, int64_t BL, int io_dtype, int* path);
 /* Kernel launches aimet_bq_encode_qdq has issued in this process; reset != 0 zeroes it. */
 int aimet_bq_launch_count(int64_t* count, int reset);
 
+/* ---- Learned blockwise ranges (csrc/lg_block.hip) ---------------------------------------------------
+ * The learned-grid forward / backward (aimet_lg_forward_range / aimet_lg_backward: the arithmetic of
+ * quantsim_straight_through_grad.py:121-328, element by element) over a contiguous float32 weight
+ * viewed as [E][BL], block e with its own trainable range (encoding_min[e], encoding_max[e]); E in
+ * [channel][block] order as aimet_bq_encode_qdq's table, E < 2^31, 1 <= BL <= AIMET_LG_BLOCK_MAX_BL
+ * (longer blocks are per-channel rows: aimet_lg_forward_range with outer = 1, C = E, K = BL). One launch
+ * each, no scratch, no atomics; results do not change from run to run.
+ *   forward:  y (out_dtype 0 float32, 1 float16, 2 bfloat16: the float32 result cast once, as torch's
+ *             .to) and enc[4][E] = {delta, offset, encoding_min, encoding_max as read} for the backward.
+ *   backward: grad of grad_dtype (16-bit values are upcast, exact); grad_x = mask * grad in float32
+ *             (NULL: not stored); grad_min[e], grad_max[e] from the block's sums {A, B, D} by
+ *             aimet_lg_range_spec's expressions. mode: 0 symmetric signed, 1 symmetric unsigned,
+ *             2 asymmetric; num_steps as the forward's grid (2^bw - 1, one less for strict symmetric).
+ * Pointers need the alignment of their element type only (16-byte aligned x / y / grad_x, 8-byte
+ * aligned 16-bit y / grad and BL % 4 == 0 take the vector path; anything else the element path of the
+ * same kernels, with the same results). E == 0 succeeds and writes nothing; an invalid shape or dtype,
+ * a null or a host pointer is AIMET_ERR_INVALID_ARGUMENT and nothing is written. */
+#define AIMET_LG_BLOCK_MAX_BL 1024
+int aimet_lg_block_forward(const float* x, void* y, int64_t E, int64_t BL, int out_dtype,
+                           const float* encoding_min_dev, const float* encoding_max_dev, int bitwidth,
+                           int use_symmetric, int use_strict_symmetric, int is_unsigned_symmetric, float* enc,
+                           void* stream);
+int aimet_lg_block_backward(const float* x, const void* grad, int grad_dtype, float* grad_x, int64_t E, int64_t BL,
+                            const float* enc, float num_steps, int mode, float* grad_min_dev, float* grad_max_dev,
+                            void* stream);
+/* The blocks one trip of the kernels' fixed grid covers for this block length (a tensor of more blocks
+ * is looped over in address order). */
+int aimet_lg_block_round(int64_t BL, int out_dtype, int64_t* blocks);
+
 #ifdef __cplusplus
 }
 #endif
