@@ -290,6 +290,10 @@ _PROTOTYPES = {
     "aimet_lg_block_forward": [_vp, _vp, _i64, _i64, _int, _vp, _vp, _int, _int, _int, _int, _vp, _vp],
     "aimet_lg_block_backward": [_vp, _vp, _int, _vp, _i64, _i64, _vp, ctypes.c_float, _int, _vp, _vp, _vp],
     "aimet_lg_block_round": [_i64, _int, _i64p],
+    "aimet_mx_qdq": [_vp, _vp, _i64, _i64, _i64, _int, _int, _vp],
+    "aimet_mx_quantize": [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp],
+    "aimet_mx_dequantize": [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp],
+    "aimet_mx_launch_count": [_i64p, _int],
 }
 _RESTYPES = {"aimet_last_error": ctypes.c_char_p, "aimet_version": ctypes.c_char_p,
              "aimet_attn_softmax_max_s": ctypes.c_int64}

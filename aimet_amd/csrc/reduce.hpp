@@ -12,6 +12,7 @@
 //                                every lane of a group gets the group's result. v is a 4- or 8-byte
 //                                arithmetic value, or a trivially copyable record of 4-byte words
 //                                (several values side by side: one loop, one op over the record)
+//   quad_all(word, op)           the same over aligned groups of 4 lanes, one 32-bit word, two DPP steps
 //   wave_best(rec, better)       butterfly that keeps `other` where better(other, rec)
 //   block_fold_own<W>            wave_all, lane 0 of each wave to lds[wave], one barrier, thread 0
 //                                starts from its own value and folds waves 1..W-1
@@ -58,6 +59,17 @@ __device__ __forceinline__ T wave_all(T v, Op op, int span = 64)
     for (int d = 32; d > 0; d >>= 1)
         if (d < span)
             v = op(v, lane_xor(v, d));
+    return v;
+}
+
+// wave_all over aligned groups of 4 lanes for one 32-bit word, as two DPP quad_perm moves
+// ([1,0,3,2] then [2,3,0,1]) instead of two trips through the LDS crossbar. The four lanes of a
+// group must be active together.
+template <class Op>
+__device__ __forceinline__ uint32_t quad_all(uint32_t v, Op op)
+{
+    v = op(v, (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0xB1, 0xF, 0xF, true));
+    v = op(v, (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x4E, 0xF, 0xF, true));
     return v;
 }
 

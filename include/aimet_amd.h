@@ -1156,6 +1156,37 @@ int aimet_lg_block_backward(const float* x, const void* grad, int grad_dtype, fl
  * is looped over in address order). */
 int aimet_lg_block_round(int64_t BL, int out_dtype, int64_t* blocks);
 
+/* ---- OCP Microscaling fake-quantization (csrc/mx.hip) -------------------------------------------------
+ * MXFP8 / MXFP6 / MXFP4: blocks of 32 values along K of a contiguous tensor viewed as [outer][K][inner]
+ * (K % 32 == 0) share a power-of-two scale 2^s taken from the block's own maximum at every call:
+ * s = clamp(floor(log2 max|v|) - emax, -127, 127), elements rounded to nearest even on the format's grid
+ * (subnormals included) and saturated at its max normal; a block with a NaN or an Inf is all NaN. The full
+ * contract is the header comment of csrc/mx.hip; the results equal its float64 restatement bit for bit.
+ * io_dtype 0 = float32, 1 = float16, 2 = bfloat16 (the float32 result rounded once). One launch each.
+ *   aimet_mx_qdq: out (may be in; may not overlap it otherwise) = the quantize-dequantized tensor.
+ *     inner == 1 takes the row form (16-byte aligned in / out: vector accesses, otherwise element
+ *     accesses with the same results), inner > 1 the column form.
+ *   aimet_mx_quantize: the packed form of a [rows][K] tensor: scales [rows][K / 32] bytes (s + 127; 0xFF for
+ *     a NaN block, whose codes are zero) and codes [rows][K w / 8] bytes, w = 8, 6 or 4 bits an element,
+ *     element i of a block at bits [w i, w i + w) of the block's little-endian bit string, a code being
+ *     sign, exponent, mantissa in the OCP encoding. codes must be 8-byte aligned.
+ *   aimet_mx_dequantize: the inverse; dequantize(quantize(x)) is aimet_mx_qdq(x) bit for bit.
+ * K % 32 != 0, an unknown format or io_dtype, a non-positive size, a null or a host pointer is
+ * AIMET_ERR_INVALID_ARGUMENT and nothing is written. */
+#define AIMET_MX_FP8_E4M3 0
+#define AIMET_MX_FP8_E5M2 1
+#define AIMET_MX_FP6_E3M2 2
+#define AIMET_MX_FP6_E2M3 3
+#define AIMET_MX_FP4_E2M1 4
+int aimet_mx_qdq(const void* in, void* out, int64_t outer, int64_t K, int64_t inner, int io_dtype, int format,
+                 void* stream);
+int aimet_mx_quantize(const void* in, uint8_t* scales, uint8_t* codes, int64_t rows, int64_t K, int io_dtype,
+                      int format, void* stream);
+int aimet_mx_dequantize(const uint8_t* scales, const uint8_t* codes, void* out, int64_t rows, int64_t K, int io_dtype,
+                        int format, void* stream);
+/* Kernel launches of the three entry points above in this process; reset != 0 zeroes it. */
+int aimet_mx_launch_count(int64_t* count, int reset);
+
 #ifdef __cplusplus
 }
 #endif
