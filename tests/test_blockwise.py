@@ -286,6 +286,45 @@ def test_block_permute_and_fp16_on_device():
         np.testing.assert_array_equal(bits(y), bits(O.qdq_fp16(x[off:])))
 
 
+@pytest.mark.gpu
+@gpu
+def test_scalar_broadcast_and_permute_past_the_grid_cap():
+    """bcast_scalar_kernel and permute_kernel (broadcast.hip:415, :428) run an element a lane under
+    stream_blocks' cap of 2048 workgroups (common.hpp:28, :109) of 256 lanes: 524295 = 191 x 61 x 45
+    elements send the first 7 lanes on a second trip. Blocks of 45 (the innermost run is no multiple of
+    4: the scalar kernel); outputs hold NaN before the launch."""
+    import torch
+    from aimet_amd import _native
+    from aimet_amd.onnx_op import BroadcastShapeInfo
+    cap = 2048 * 256
+    rng = np.random.default_rng(12)
+    stream = torch.cuda.current_stream().cuda_stream
+    # contiguous blocks of 45 along axis 1
+    info = BroadcastShapeInfo((191, 2745), 0, 1, 45)
+    n, E, nd = info.numElements, info.numEncodings, info.numDims
+    assert n == cap + 7 and info.tensorShape[-1] % 4 != 0
+    x = (rng.standard_normal(n) * 0.05).astype(np.float32)
+    mx = rng.uniform(0.01, 0.2, E).astype(np.float32)
+    d = (mx / 7).astype(np.float32)
+    tab = np.stack([-8 * d, mx, d, np.full(E, -8, np.float32)])
+    want = O.qdq_broadcast(x, info.tensorStrides, info.encodingStrides, *tab)
+    xt, yt, tt = torch.from_numpy(x).cuda(), torch.full((n,), np.nan, device="cuda"), torch.from_numpy(tab).cuda()
+    _native.call("aimet_qdq_broadcast", xt.data_ptr(), yt.data_ptr(), n, nd, (ctypes.c_int64 * nd)(*info.tensorStrides),
+                 (ctypes.c_int64 * nd)(*info.encodingStrides), *[t.data_ptr() for t in tt], stream)
+    got = yt.cpu().numpy()
+    np.testing.assert_array_equal(bits(got[cap:]), bits(want[cap:]))
+    np.testing.assert_array_equal(bits(got), bits(want))
+    # strided blocks of 45 along axis 0 made contiguous
+    shape = ((2745, 191), 1, 0, 45)
+    info = BroadcastShapeInfo(*shape)
+    assert info.numElements == n and not info.hasContiguousBlocks()
+    want = O.copy_to_contiguous_block_layout(x, O.broadcast_shape_info(*shape))
+    assert not np.array_equal(want, x)
+    yt.fill_(np.nan)
+    _native.call("aimet_copy_to_contiguous_block_layout", xt.data_ptr(), yt.data_ptr(), ctypes.byref(info._c), stream)
+    np.testing.assert_array_equal(bits(yt.cpu().numpy()), bits(want))
+
+
 def _info(encs, quantizers, mode, sym=False, per_channel=False, ch=0, ba=0, bs=0, enabled=True, is_int=True):
     from aimet_amd.onnx_op import QcQuantizeInfo
     q = QcQuantizeInfo()

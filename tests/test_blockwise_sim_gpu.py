@@ -105,6 +105,65 @@ def test_kernel_paths(dtype, NB, BL, R, path):
         np.testing.assert_array_equal(raw(got_y), want_y, err_msg=place)
 
 
+# blockwise.hip:53 caps the grid at kMaxGrid = 65536 workgroups; bq_wave gives a workgroup four rows
+# (kBlk / kWave, blockwise.hip:217), bq_group one. A row past these strides is a second trip of the row
+# loop (blockwise.hip:218, :312), over a block table in LDS that the first trip filled.
+MAX_GRID = 1 << 16
+WAVE_ROWS = 4
+TILE = 257   # a prime that divides neither stride: rows one stride apart never hold equal data
+SENTINEL = -777.25   # no 4-bit grid of these blocks reaches it; a 16-bit type rounds it, and compares as rounded
+
+
+# The vector slots a lane of bq_wave holds (plan_of, blockwise.hip:435) choose the instantiation: a block of
+# 16 elements takes 4 lanes (fp32) or 8 (16-bit), so a wave covers 16 or 8 blocks a round and NB = 1 is
+# <IO, 1>, NB = 9 in bf16 two rounds, <IO, 2>. At BL = 16, the shortest block the suite uses, 64 bf16 blocks
+# are the wave path's last row (8 rounds) and 65 the group path's first.
+@pytest.mark.parametrize("dtype,NB,path,stride,shift", [("fp32", 1, "PATH_WAVE", MAX_GRID * WAVE_ROWS, 1),
+                                                        ("bf16", 1, "PATH_WAVE", MAX_GRID * WAVE_ROWS, 0),
+                                                        ("bf16", 9, "PATH_WAVE", MAX_GRID * WAVE_ROWS, 1),
+                                                        ("bf16", 65, "PATH_GROUP", MAX_GRID, 1)],
+                         ids=["wave1-fp32", "wave1-bf16", "wave2-bf16", "group-bf16"])
+def test_rows_past_the_grid_cap(dtype, NB, path, stride, shift):
+    """The second trip of the grid-stride row loop of bq_wave<IO, 1>, bq_wave<IO, 2> and bq_group<IO, true>:
+    three rows more than the capped grid covers in one trip, out of place into a table and an output that
+    hold a sentinel, the base `shift` elements past 16 bytes. The host restatement runs on TILE distinct
+    rows, among them an all-zero and a constant block; row r of the tensor is row r mod TILE of them, and
+    the two special rows are the first two past the cap.
+
+    bq_group<IO, false> (PATH_TWO_PASS) is not here. Its smallest row is 1023 bf16 blocks of 16 elements,
+    32736 bytes (the 64 KiB of LDS less 32 bytes a block, at most 1024 blocks a row), so the 65537 rows
+    of a second trip are 2.1 GB, and 1 GB of such rows is 30547 rows: no second trip."""
+    from aimet_amd import _native, blockwise as B
+    BL, bw, flags = 16, 4, SYMMETRY["asymmetric"]
+    td = DTYPES[dtype]
+    assert B.row_path(NB, BL, td) == getattr(B, path) and stride % TILE != 0
+    if NB == 65:
+        assert B.row_path(NB - 1, BL, td) == B.PATH_WAVE
+    R = stride + 3
+    rng = np.random.default_rng(NB)
+    x, x32 = data(rng, TILE * NB * BL, td)
+    x, x32 = x.view(TILE, NB, BL), x32.reshape(TILE, NB, BL)
+    x[stride % TILE, 0], x32[stride % TILE, 0] = 0.0, 0.0
+    x[(stride + 1) % TILE, NB - 1], x32[(stride + 1) % TILE, NB - 1] = 1.25, 1.25
+    want_t = table_of(host_encodings(x32.ravel(), TILE * NB, BL, bw, *flags))
+    want_y = host_qdq(x32.ravel(), want_t, td).view(TILE, NB * BL)
+    tile = torch.arange(R) % TILE
+    want_t = torch.from_numpy(want_t).view(4, TILE, NB)[:, tile].reshape(4, R * NB)
+    want_y = want_y[tile].ravel()
+    n = R * NB * BL
+    src = torch.empty(n + 1, dtype=td, device="cuda")[shift:shift + n].copy_(x.view(TILE, NB * BL)[tile].ravel())
+    dst = torch.full((n + 1,), SENTINEL, dtype=td, device="cuda")[shift:shift + n]
+    table = torch.full((4, R * NB), SENTINEL, dtype=torch.float32, device="cuda")
+    _native.call("aimet_bq_encode_qdq", src.data_ptr(), dst.data_ptr(), R, NB, BL, _native.IO_CODES[td], bw,
+                 *(int(f) for f in flags), 0, table.data_ptr(), None, None, torch.cuda.current_stream().cuda_stream)
+    got_t, got_y = table.cpu(), dst.cpu()
+    # the second trip first: rows it leaves unwritten hold the sentinel
+    np.testing.assert_array_equal(raw(got_y[stride * NB * BL:]), raw(want_y[stride * NB * BL:]))
+    np.testing.assert_array_equal(raw(got_t[:, stride * NB:]), raw(want_t[:, stride * NB:]))
+    assert np.array_equal(raw(got_y), raw(want_y))
+    assert np.array_equal(raw(got_t), raw(want_t))
+
+
 @pytest.mark.parametrize("sym", list(SYMMETRY))
 def test_kernel_degenerate_blocks(sym):
     """Blocks that are all zero, all positive, all negative and constant, among random ones."""

@@ -538,6 +538,42 @@ def test_adaround_backward_grid_forms_equal(reg, n, C, exact_pow):
         assert loss.item() > 0.0
 
 
+def test_adaround_scalar_kernels_past_the_grid_cap():
+    """adaround_fwd_kernel and adaround_bwd_kernel (adaround.hip:1194, :1277; K % 4 != 0) run an element
+    a lane under stream_blocks' cap of 2048 workgroups (common.hpp:28, :109) of 256 lanes: [32, 16385]
+    sends the first 32 lanes on a second trip (numel stays a multiple of 32, so every element takes
+    torch's vectorized sigmoid). Wq and dL/dalpha (no rounding loss: no pow) vs torch autograd of the
+    reference formula on the CPU, bit for bit; the outputs hold NaN before the launch."""
+    from aimet_amd import _native
+    from oracle import torch_ref as T
+    C, K, cap = 32, 16385, 2048 * 256
+    n = C * K
+    assert n == cap + 32 and K % 4 != 0
+    gen = torch.Generator().manual_seed(6)
+    w = torch.randn(C, K, generator=gen) * 0.1
+    delta = torch.rand(C, generator=gen) * 0.01 + 0.001
+    offset = torch.full((C,), -128.0)
+    alpha = torch.randn(C, K, generator=gen)
+    g = torch.randn(C, K, generator=gen)
+
+    def ref():
+        a = alpha.clone().requires_grad_(True)
+        wq = T.adaround_forward(w, a, delta.view(C, 1), offset.view(C, 1), 8)
+        (wq * g).sum().backward()
+        return wq.detach(), a.grad
+    wq_ref, ga_ref = _cpu_one_thread(ref)
+    w_d, alpha_d, g_d, delta_d, offset_d = (t.to(DEV) for t in (w, alpha, g, delta, offset))
+    wq, ga = (torch.full((C, K), float("nan"), device=DEV) for _ in range(2))
+    stream = torch.cuda.current_stream().cuda_stream
+    _native.call("aimet_adaround_forward", w_d.data_ptr(), alpha_d.data_ptr(), wq.data_ptr(), 1, C, K,
+                 delta_d.data_ptr(), offset_d.data_ptr(), 8, 1, stream)
+    _native.call("aimet_adaround_backward", w_d.data_ptr(), alpha_d.data_ptr(), g_d.data_ptr(), ga.data_ptr(), 1, C, K,
+                 delta_d.data_ptr(), offset_d.data_ptr(), 8, ctypes.c_double(0.0), ctypes.c_double(0.0), None, stream)
+    for got, want in ((wq.cpu(), wq_ref), (ga.cpu(), ga_ref)):
+        assert torch.equal(got.view(-1)[cap:], want.view(-1)[cap:])
+        assert torch.equal(got, want)
+
+
 def test_adaround_hard_rounding_floor_exact_at_multiples():
     """floor(W / delta) in the AdaRound kernels (reciprocal fast path, adaround.hip: floor_div) equals
     torch's IEEE floor(W / delta) bit for bit, on weights at exact multiples of delta and 1-2 ulp
@@ -1206,6 +1242,31 @@ def test_recon_loss_backward_fused_vs_torch(act, shape):
     a, b = (act(qb), act(t)) if act is not None else (qb, t)
     recon_loss(a, b).backward()
     torch.testing.assert_close(qa.grad, qb.grad, rtol=2e-6, atol=1e-12)
+
+
+def test_recon_grad_scalar_kernel_past_the_grid_cap():
+    """recon_grad_kernel (adaround.hip:1332) takes the whole tensor when a base is off 16 bytes, an
+    element a lane under stream_blocks' cap of 2048 workgroups (common.hpp:28, :109) of 256 lanes:
+    [3, 174763] sends lane 0 on a second trip. Against torch autograd of recon_loss as the test above,
+    the gradient holding NaN before the launch."""
+    from aimet_amd import _native
+    from aimet_amd.adaround_optimizer import recon_loss
+    shape, cap = (3, 174763), 2048 * 256
+    n = shape[0] * shape[1]
+    assert n == cap + 1
+    g = torch.Generator(device=DEV).manual_seed(8)
+    q, t, grad = (torch.full((n + 1,), float("nan"), device=DEV)[1:].view(shape) for _ in range(3))
+    assert q.data_ptr() % 16 == 4
+    q.copy_(torch.randn(*shape, device=DEV, generator=g) * 4)
+    t.copy_(q + torch.randn(*shape, device=DEV, generator=g))
+    q.view(-1)[-3:] = torch.tensor([0.0, 6.0, -0.0], device=DEV)   # activation edges, the last on the second trip
+    _native.call("aimet_adaround_recon_grad", q.data_ptr(), t.data_ptr(), grad.data_ptr(), n, shape[1], 2,
+                 torch.cuda.current_stream().cuda_stream)
+    qb = q.clone().requires_grad_(True)
+    act = torch.nn.ReLU6()
+    recon_loss(act(qb), act(t)).backward()
+    torch.testing.assert_close(grad.view(-1)[cap:], qb.grad.view(-1)[cap:], rtol=2e-6, atol=1e-12)
+    torch.testing.assert_close(grad, qb.grad, rtol=2e-6, atol=1e-12)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])

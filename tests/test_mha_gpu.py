@@ -5,7 +5,7 @@ QuantSim integration) against tests/mha_oracle.py and tests/golden/golden_mha.np
    taken (the 64-column steps of the wave path's instantiations, the wave / LDS boundary at 1024, the
    resident bound), L in {1, 3}, B = 2, H = 3, five mask layouts x four encoding layouts, bases
    aligned and off by one float, in place and out of place; a fully masked row; the refusal past
-   the resident bound;
+   the resident bound; more rows than the capped grid takes in one trip;
 2. the module in ACTIVE mode against the fixture written from the reference, bit for bit, on the fused
    route and with fused = False;
 3. ANALYSIS mode: the two fused quantizers' encodings against fresh quantizers fed the raw scores and
@@ -151,6 +151,58 @@ def test_a_row_past_the_resident_bound_is_refused_and_nothing_is_written():
         T.attn_softmax(scores, 1, 1, out=dst.view(1, 1, S))
     assert T.attn_launch_count() == n
     assert np.array_equal(dst.bits(), dst.expect(np.full(S, SENTINEL, F)))
+
+
+# attn_softmax.hip:56 caps the grid at kMaxGrid = 65536 workgroups; the wave path gives a workgroup four
+# rows (kBlk / kWave, attn_softmax.hip:144), the LDS path one. A row index past these strides is a
+# lane's second trip of the row loop (attn_softmax.hip:145, :185).
+MAX_GRID = 1 << 16
+WAVE_ROWS = 4
+TILE = 257   # a prime that divides neither stride: rows one stride apart never hold equal data
+
+
+# B H = 6 divides the row count, so the remainder past the cap is even: L is the smallest with two rows
+# left over. On the wave path they are waves 0 and 1 of workgroup 0; waves 2 and 3 make one trip.
+@pytest.mark.parametrize("S,per_lane,stride,in_place",
+                         [(37, 1, MAX_GRID * WAVE_ROWS, False), (67, 2, MAX_GRID * WAVE_ROWS, False),
+                          (1025, None, MAX_GRID, True)], ids=["wave1", "wave2", "lds"])
+def test_rows_past_the_grid_cap_equal_the_oracle_bit_for_bit(S, per_lane, stride, in_place):
+    """The second trip of the grid-stride row loop: attn_softmax_wave<1>, <2> (the other instantiations
+    share the loop) and attn_softmax_lds with two rows more than the capped grid covers in one trip,
+    per-matrix and padding masks and both encodings; a misaligned destination between sentinel guards.
+    The oracle runs on TILE distinct rows under either batch's padding mask; row r of the tensor is row
+    r mod TILE of them. The first row past the cap is fully masked."""
+    if per_lane is None:
+        assert O.WAVE_MAX_S < S <= T.attn_softmax_max_s() and stride == MAX_GRID
+    else:   # ceil(S / 64) values a lane choose the instantiation
+        assert -(-S // O.WAVE) == per_lane and stride == MAX_GRID * WAVE_ROWS
+    assert stride % TILE != 0
+    L =stride // (B * H) + 1
+    rows = B * H * L
+    assert stride < rows == stride + 2
+    rng = np.random.default_rng(S)
+    base = (rng.standard_normal((TILE, S)) * 3.0).astype(F)
+    base_am, kpm = rng.random((TILE, S)) < 0.3, rng.random((B, S)) < 0.3
+    base_am[:, 0] = kpm[:, 0] = False
+    base_am[stride % TILE] = True
+    # want[b, p]: row p of the base in batch b
+    want = O.attn_softmax(np.stack([base] * B), B, 1, TILE, S, np.stack([base_am] * B), True, kpm, SCORE_ENC, PROB_ENC)
+    tile, batch = np.arange(rows) % TILE, np.arange(rows) // (H * L)
+    assert tile[stride] == stride % TILE and batch[stride] == B - 1
+    # min(NaN, max) = max: the masked row quantizes to the grid's upper end (the test above)
+    assert np.array_equal(want[B - 1, tile[stride]], O.qdq(np.full(S, np.nan, F), PROB_ENC))
+    scores, want = base[tile], want[batch, tile]
+    am_d, kpm_d = _dev(base_am[tile].reshape(B * H, L, S)), _dev(kpm)
+    src = Guarded(scores.size, True, scores)
+    dst = src if in_place else Guarded(scores.size, True)
+    T.attn_softmax(src.view(B * H, L, S), B, H, am_d, kpm_d, SCORE_ENC, PROB_ENC, out=dst.view(B * H, L, S))
+    got, expect = dst.bits(), dst.expect(want)
+    # the second trip first: rows it leaves unwritten hold the sentinel (the scores, in place)
+    tail = slice(dst.lead + stride * S, dst.lead + rows * S)
+    assert np.array_equal(got[tail], expect[tail])
+    assert np.array_equal(got, expect)
+    if not in_place:
+        assert np.array_equal(src.bits(), src.expect(scores))
 
 
 # ---- 2. the module in ACTIVE mode against the reference fixture --------------------------------------

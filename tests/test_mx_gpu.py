@@ -141,6 +141,90 @@ def test_pack_unpack(fmt, dtype, rows, K):
         assert back.dtype == dtype and same(back, mx_quantize_dequantize(dev, fmt)) and same(back, ref_qdq(x, fmt))
 
 
+# stream_blocks (common.hpp:109) caps these launches at kMaxStreamBlocks = 2048 workgroups (common.hpp:28)
+# of kBlock = 256 lanes: lane slots (8 elements of the row kernels, a block of the column kernel) past
+# 524288 are a second trip of the loop (MX_ROW_LOOP, mx.hip:225; mx.hip:318).
+MAX_SLOTS = 2048 * 256
+TILE = 257   # a prime that divides neither stride: blocks one stride apart never hold equal data
+SENTINEL = -777.25   # more significant bits than any element format has, also once a 16-bit type rounded it
+
+
+def tiled_blocks(fmt, dtype, first_past, blocks):
+    """`blocks` blocks of 32, block i being block i mod TILE of TILE distinct ones: (the distinct ones
+    [TILE, 32], i mod TILE [blocks]). Blocks `first_past` .. `first_past` + 3 are a NaN block, a zero
+    block, an Inf block and the grid block."""
+    assert first_past % TILE != 0 and first_past < blocks
+    base = variants((TILE, 32, 1), fmt, dtype, seed=first_past)[0].squeeze(-1)   # the variant with a zero block
+    g = torch.Generator().manual_seed(1)
+    nan, inf = (torch.randn(32, generator=g, dtype=torch.float64) for _ in range(2))
+    nan[17], inf[30] = float("nan"), float("-inf")
+    special = [nan, torch.zeros(32, dtype=torch.float64), inf, grid_block(fmt)]
+    for i, block in enumerate(special):
+        base[(first_past + i) % TILE] = block.to(dtype)
+    return base, torch.arange(blocks) % TILE
+
+
+def row_kernels_past_the_grid_cap(dtype):
+    """The second trip of MX_ROW_LOOP in mx_row_qdq, mx_row_pack and mx_row_unpack: 12 lane slots (three
+    blocks) more than the capped grid covers in one trip, every output holding a sentinel before the
+    launch. The reference runs on TILE distinct blocks; the first blocks past the cap are the special ones."""
+    from aimet_amd import _native
+    fmt, K, k = MxFormat.MXFP4_E2M1, 32, 3
+    rows = (MAX_SLOTS + 4 * k) // 4
+    n = rows * K
+    assert n // 8 == MAX_SLOTS + 4 * k and MAX_SLOTS % TILE != 0
+    base, tile = tiled_blocks(fmt, dtype, MAX_SLOTS // 4, rows)
+    want = ref_qdq(base, fmt)[tile]
+    scales, codes = (torch.from_numpy(a)[tile] for a in ref_pack(base, fmt))
+    past = MAX_SLOTS // 4   # the first row of the second trip
+    assert want[past].isnan().all() and not want[past + 1].any() and want[past + 2].isnan().all()
+    dev = base[tile].cuda()
+    stream, io = torch.cuda.current_stream().cuda_stream, _native.IO_CODES[dtype]
+
+    out = torch.full_like(dev, SENTINEL)
+    assert mx_quantize_dequantize(dev, fmt, out=out) is out
+    assert same(out[past:], want[past:]) and same(out, want)
+
+    got_scales, got_codes = torch.full_like(scales, 0xA5).cuda(), torch.full_like(codes, 0xA5).cuda()
+    assert not (scales == 0xA5).any() and not (codes.view(torch.int32) == 0xA5A5A5A5 - (1 << 32)).any()
+    _native.call("aimet_mx_quantize", dev.data_ptr(), got_scales.data_ptr(), got_codes.data_ptr(), rows, K, io,
+                 fmt.value, stream)
+    assert torch.equal(got_scales.cpu()[past:], scales[past:]) and torch.equal(got_scales.cpu(), scales)
+    assert torch.equal(got_codes.cpu()[past:], codes[past:]) and torch.equal(got_codes.cpu(), codes)
+
+    back = torch.full_like(dev, SENTINEL)
+    _native.call("aimet_mx_dequantize", got_scales.data_ptr(), got_codes.data_ptr(), back.data_ptr(), rows, K, io,
+                 fmt.value, stream)
+    assert same(back[past:], want[past:]) and same(back, want)
+
+
+def column_kernel_past_the_grid_cap(dtype):
+    """The second trip of mx_col_qdq's loop: a [58255, 32, 9] tensor, 7 lane slots (blocks) more
+    than the capped grid covers in one trip, into an output that holds a sentinel. Lane slot j is block
+    j mod TILE of TILE distinct ones; the first blocks past the cap are the special ones."""
+    fmt, outer, K, inner = MxFormat.MXFP8_E4M3, 58255, 32, 9
+    slots = outer * inner
+    assert slots == outer * K * inner // 32 == MAX_SLOTS + 7 and MAX_SLOTS % TILE != 0
+    base, tile = tiled_blocks(fmt, dtype, MAX_SLOTS, slots)
+
+    def spread(blocks):   # [TILE, 32] -> [outer, K, inner], slot j = (outer index, inner index)
+        return blocks[tile].view(outer, inner, K).transpose(1, 2).contiguous()
+    want = spread(ref_qdq(base, fmt))
+    dev = spread(base).cuda()
+    assert want[-1, :, 2].isnan().all() and not want[-1, :, 3].any()   # slots MAX_SLOTS and MAX_SLOTS + 1
+    out = torch.full_like(dev, SENTINEL)
+    assert mx_quantize_dequantize(dev, fmt, axis=1, out=out) is out
+    assert same(out[-1, :, 2:], want[-1, :, 2:]) and same(out, want)
+
+
+@pytest.mark.parametrize("case,dtype", [(row_kernels_past_the_grid_cap, torch.float32),
+                                        (row_kernels_past_the_grid_cap, torch.bfloat16),
+                                        (column_kernel_past_the_grid_cap, torch.bfloat16)],
+                         ids=["row-fp32", "row-bf16", "column-bf16"])
+def test_kernels_past_the_grid_cap(case, dtype):
+    case(dtype)
+
+
 class Net(torch.nn.Module):
     def __init__(self):
         super().__init__()
