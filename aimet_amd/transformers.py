@@ -26,6 +26,17 @@ exponential: the kernel's is written out in float32 operations, the literal rout
   * literal: the children called one by one. Everything else -- range learning / QAT, 16-bit or CPU
     tensors, float data types, stochastic rounding, enabled input quantizers, an unwrapped module,
     longer rows -- and `module.fused = False`.
+  * fused with a gradient (opt-in, `module.fused_backward = True` or set_fused_attention_backward(model)):
+    the fused route also when q or k needs a gradient, through AttnSoftmax. Its forward is the same
+    launch, out of place, and keeps the raw scores alone for the way back; its backward is ONE
+    aimet_attn_softmax_backward launch that recomputes each row on chip and applies both
+    straight-through masks, the softmax backward and the mask fills (the literal route keeps the raw
+    scores, the softmax output and the unquantized probabilities, and runs an STE kernel, torch's
+    softmax backward, the mask-fill backwards and a second STE kernel). Static-grid wrappers only: the
+    gradient of a calibrated sim, STE QAT with the post_training_* schemes. Range-learning wrappers
+    still take the literal route. The gradients of the two routes differ by float32 rounding and, where
+    exp_r and torch's exponential put a probability on neighbouring levels, by one level of softmax's
+    quantizer. Measured against the literal route in DESIGN section 5.
 
 Masks: bool (or, deprecated, uint8) attn_mask of [L, S] or [B H, L, S] and key_padding_mask of [B, S],
 True = not attended. nn.TransformerEncoderLayer / DecoderLayer hand their masks on as float tensors
@@ -57,6 +68,7 @@ from typing import Optional, Tuple
 import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
+from torch.autograd.function import once_differentiable
 
 from aimet_amd import _native
 from aimet_amd.elementwise_ops import Add, Divide, MatMul
@@ -78,23 +90,55 @@ def attn_launch_count(reset: bool = False) -> int:
     return n.value
 
 
+def attn_backward_launch_count(reset: bool = False) -> int:
+    """aimet_attn_softmax_backward launches issued in this process."""
+    n = ctypes.c_int64(0)
+    _native.call("aimet_attn_backward_launch_count", ctypes.byref(n), int(reset))
+    return n.value
+
+
 def _encoding_c(enc):
     """A TfEncoding, or (min, max, bitwidth) -> the C struct (delta and offset are recomputed from the
-    three, as aimet_qdq_per_tensor does)."""
-    if enc is None:
-        return None
+    three, as aimet_qdq_per_tensor does); a C struct is handed on."""
+    if enc is None or isinstance(enc, _native.TfEncodingC):
+        return enc
     if isinstance(enc, (tuple, list)):
         return _native.TfEncodingC(float(enc[0]), float(enc[1]), 0.0, 0.0, int(enc[2]))
     return _native.TfEncodingC(enc.min, enc.max, enc.delta, enc.offset, enc.bw)
 
 
-def _mask_bytes(mask, shape, device, what):
+def _mask_bytes(mask, shape, device, what, fn):
     if mask is None:
         return None
     if mask.dtype != torch.bool or tuple(mask.shape) != tuple(shape) or mask.device != device:
-        raise ValueError("attn_softmax: %s must be a bool tensor of shape %s on %s, got %s %s on %s"
+        raise ValueError(fn + ": %s must be a bool tensor of shape %s on %s, got %s %s on %s"
                          % (what, tuple(shape), device, mask.dtype, tuple(mask.shape), mask.device))
     return mask.contiguous().view(torch.uint8)
+
+
+def _launch_args(fn, scores, batch, num_heads, attn_mask, key_padding_mask, score_enc, prob_enc, others):
+    """The checks attn_softmax and attn_softmax_backward share -> (the arguments after the float tensors,
+    the objects they point into). `fn` names the caller in the errors; `others`: name -> the float
+    tensors that must match scores (None: a new one)."""
+    if not (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 3 and scores.is_contiguous()):
+        raise ValueError(fn + ": scores must be a contiguous float32 [B H, L, S] tensor on the GPU")
+    BH, L, S = scores.shape
+    if BH != batch * num_heads:
+        raise ValueError(fn + ": scores has %d matrices, batch * num_heads is %d" % (BH, batch * num_heads))
+    for name, t in others.items():
+        if t is None:
+            others[name] = torch.empty_like(scores)
+        elif not (t.is_cuda and t.dtype == torch.float32 and t.shape == scores.shape and t.is_contiguous() and
+                  t.device == scores.device):
+            raise ValueError(fn + ": %s must match scores" % name)
+    per_bh = attn_mask is not None and attn_mask.dim() == 3
+    am = _mask_bytes(attn_mask, (BH, L, S) if per_bh else (L, S), scores.device, "attn_mask", fn)
+    kpm = _mask_bytes(key_padding_mask, (batch, S), scores.device, "key_padding_mask", fn)
+    s_enc, p_enc = _encoding_c(score_enc), _encoding_c(prob_enc)
+    args = (batch, num_heads, L, S, am.data_ptr() if am is not None else None, int(per_bh),
+            kpm.data_ptr() if kpm is not None else None, ctypes.byref(s_enc) if s_enc is not None else None,
+            ctypes.byref(p_enc) if p_enc is not None else None)
+    return args, (am, kpm, s_enc, p_enc)
 
 
 def attn_softmax(scores: Tensor, batch: int, num_heads: int, attn_mask: Optional[Tensor] = None,
@@ -104,28 +148,58 @@ def attn_softmax(scores: Tensor, batch: int, num_heads: int, attn_mask: Optional
     QDQ(score_enc), masks (attn_mask [L, S] or [batch * num_heads, L, S], key_padding_mask
     [batch, S]; bool, True = -inf), softmax, QDQ(prob_enc). Encodings: TfEncoding, (min, max, bw) or
     None. `out` may be `scores`. There is no other implementation behind this function."""
-    if not (scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 3 and scores.is_contiguous()):
-        raise ValueError("attn_softmax: scores must be a contiguous float32 [B H, L, S] tensor on the GPU")
-    BH, L, S = scores.shape
-    if BH != batch * num_heads:
-        raise ValueError("attn_softmax: scores has %d matrices, batch * num_heads is %d" % (BH, batch * num_heads))
-    if out is None:
-        out = torch.empty_like(scores)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.shape == scores.shape and out.is_contiguous() and
-              out.device == scores.device):
-        raise ValueError("attn_softmax: out must match scores")
-    per_bh = attn_mask is not None and attn_mask.dim() == 3
-    am = _mask_bytes(attn_mask, (BH, L, S) if per_bh else (L, S), scores.device, "attn_mask")
-    kpm = _mask_bytes(key_padding_mask, (batch, S), scores.device, "key_padding_mask")
-    s_enc, p_enc = _encoding_c(score_enc), _encoding_c(prob_enc)
+    others = {"out": out}
+    args, _alive = _launch_args("attn_softmax", scores, batch, num_heads, attn_mask, key_padding_mask, score_enc,
+                                prob_enc, others)
     with torch.cuda.device(scores.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _native.call("aimet_attn_softmax", scores.data_ptr(), out.data_ptr(), batch, num_heads, L, S,
-                     am.data_ptr() if am is not None else None, int(per_bh),
-                     kpm.data_ptr() if kpm is not None else None,
-                     ctypes.byref(s_enc) if s_enc is not None else None,
-                     ctypes.byref(p_enc) if p_enc is not None else None, stream)
-    return out
+        _native.call("aimet_attn_softmax", scores.data_ptr(), others["out"].data_ptr(), *args, stream)
+    return others["out"]
+
+
+def attn_softmax_backward(scores: Tensor, grad_probs: Tensor, batch: int, num_heads: int,
+                          attn_mask: Optional[Tensor] = None, key_padding_mask: Optional[Tensor] = None,
+                          score_enc=None, prob_enc=None, out: Optional[Tensor] = None) -> Tensor:
+    """One aimet_attn_softmax_backward launch: the gradient at the raw `scores` that attn_softmax read,
+    from `grad_probs`, the gradient at what it returned (masks and encodings as given to attn_softmax;
+    the encodings act as straight-through masks on the raw score and on the unquantized probability,
+    a masked position gets exactly 0). `out` may be `grad_probs`. There is no other implementation
+    behind this function."""
+    if grad_probs is None:
+        raise ValueError("attn_softmax_backward: grad_probs must match scores")
+    others = {"grad_probs": grad_probs, "out": out}
+    args, _alive = _launch_args("attn_softmax_backward", scores, batch, num_heads, attn_mask, key_padding_mask,
+                                score_enc, prob_enc, others)
+    with torch.cuda.device(scores.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _native.call("aimet_attn_softmax_backward", scores.data_ptr(), grad_probs.data_ptr(),
+                     others["out"].data_ptr(), *args, stream)
+    return others["out"]
+
+
+class AttnSoftmax(torch.autograd.Function):
+    """attn_softmax with a gradient for `scores`: apply(scores, batch, num_heads, attn_mask,
+    key_padding_mask, score_enc, prob_enc). The forward is one out-of-place launch and saves the raw
+    scores; the encodings are copied at the forward, so the backward sees the grid the forward used.
+    The masks are saved beside the scores (no copy), so autograd refuses the backward if scores or a
+    mask was written in place after the forward. Differentiable once: the backward is a launch autograd
+    does not see into, and a second derivative raises."""
+
+    @staticmethod
+    def forward(ctx, scores, batch, num_heads, attn_mask, key_padding_mask, score_enc, prob_enc):
+        ctx.args = (batch, num_heads, _encoding_c(score_enc), _encoding_c(prob_enc))
+        ctx.save_for_backward(scores, attn_mask, key_padding_mask)
+        return attn_softmax(scores, batch, num_heads, attn_mask, key_padding_mask, *ctx.args[2:])
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_probs):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        scores, attn_mask, key_padding_mask = ctx.saved_tensors
+        batch, num_heads, score_enc, prob_enc = ctx.args
+        return (attn_softmax_backward(scores, grad_probs.contiguous(), batch, num_heads, attn_mask, key_padding_mask,
+                                      score_enc, prob_enc),) + (None,) * 6
 
 
 # ---- masks ---------------------------------------------------------------------------------------
@@ -198,6 +272,12 @@ class QuantizableMultiheadAttention(nn.MultiheadAttention):
         self.matmul_2 = MatMul()
         self.softmax = nn.Softmax(dim=-1)
         self.fused = True
+        # The fused route also where a gradient is wanted (static-grid wrappers; module docstring).
+        # Opt-in. DESIGN section 5 has the training step measured against the literal route. While it is
+        # on, a forward that wants no gradient (no_grad, evaluation between steps) also goes through
+        # AttnSoftmax: out of place, one more score-size tensor than the in-place launch; turn it off
+        # for evaluation where that matters.
+        self.fused_backward = False
 
     def _get_name(self):
         return "QuantizableMultiheadAttention"
@@ -273,7 +353,8 @@ class QuantizableMultiheadAttention(nn.MultiheadAttention):
             return False
         if not (q.is_cuda and q.dtype == torch.float32 and k.dtype == torch.float32 and k.device == q.device):
             return False
-        if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad):
+        if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad) and \
+                not getattr(self, "fused_backward", False):
             return False
         if not (m1.output_fusable() and sm.output_fusable()):
             return False
@@ -281,11 +362,19 @@ class QuantizableMultiheadAttention(nn.MultiheadAttention):
 
     def _fused_probs(self, q, k, bsz, attn_mask, key_padding_mask):
         scores = torch.bmm(q, k.transpose(1, 2))
+        if attn_mask is not None and attn_mask.shape[0] == 1:
+            attn_mask = attn_mask[0]   # one [L, S] table for every batch entry and head
+        if getattr(self, "fused_backward", False):
+            # the statistics (ANALYSIS) see the tensors outside the graph; never in place
+            score_enc = self.matmul_1.fused_output_encoding()
+            self.matmul_1.observe_output(scores.detach())
+            prob_enc = self.softmax.fused_output_encoding()
+            probs = AttnSoftmax.apply(scores, bsz, self.num_heads, attn_mask, key_padding_mask, score_enc, prob_enc)
+            self.softmax.observe_output(probs.detach())
+            return probs
         score_enc = self.matmul_1.fused_output_encoding()
         queued = self.matmul_1.observe_output(scores)   # ANALYSIS: the statistics may read it later
         prob_enc = self.softmax.fused_output_encoding()
-        if attn_mask is not None and attn_mask.shape[0] == 1:
-            attn_mask = attn_mask[0]   # one [L, S] table for every batch entry and head
         probs = attn_softmax(scores, bsz, self.num_heads, attn_mask, key_padding_mask, score_enc, prob_enc,
                              out=None if queued else scores)
         self.softmax.observe_output(probs)
@@ -406,6 +495,15 @@ def create_quantizable_transformer_decoder_layer(layer: nn.TransformerDecoderLay
 
 
 # ---- whole models --------------------------------------------------------------------------------
+def set_fused_attention_backward(model: nn.Module, enabled: bool = True) -> int:
+    """Sets `fused_backward` on every QuantizableMultiheadAttention of `model` (a QuantizationSimModel's
+    .model included); returns how many there are."""
+    blocks = [m for m in model.modules() if isinstance(m, QuantizableMultiheadAttention)]
+    for m in blocks:
+        m.fused_backward = bool(enabled)
+    return len(blocks)
+
+
 def prepare_pt_transformer_for_quantsim(model: nn.Module) -> None:
     """model_preparer.py:694: the functional activation of every nn.TransformerEncoderLayer /
     DecoderLayer becomes a module (a child the sim can wrap), in place."""

@@ -9,12 +9,16 @@ post_training_tf), self-attention without masks, need_weights=False, on one GPU:
 For each, the same module with `fused` on (one bmm and one aimet_attn_softmax launch for matmul_1's
 quantizer, the softmax and softmax's quantizer) and off (the children called one by one):
   * ACTIVE: one forward;
-  * ANALYSIS: one compute_encodings with a one-forward callback (what a user runs to calibrate).
+  * ANALYSIS: one compute_encodings with a one-forward callback (what a user runs to calibrate);
+  * TRAIN: one forward plus backward in ACTIVE mode with a gradient for the input and every weight,
+    `fused_backward` on (AttnSoftmax: one launch each way) and off (the default: a gradient takes the
+    literal route), with torch.cuda.max_memory_allocated over the step.
 Medians of `--runs` alternating runs with min and max (device-synchronised host clock), the largest
 output difference between the routes, and aimet_attn_softmax alone on the block's [B H, L, S] tensor:
 time per launch between two events over back-to-back launches, and the 8 bytes an element it has to
-move (one float32 read, one written) over that time as a fraction of the MI355X's 8 TB/s. One JSON line
-at the end.
+move (one float32 read, one written) over that time as a fraction of the MI355X's 8 TB/s; the same for
+aimet_attn_softmax_backward against its 12 bytes an element (scores and gradient read, gradient written).
+One JSON line at the end.
 """
 import argparse
 import json
@@ -45,15 +49,19 @@ def timed(fn):
     return (time.perf_counter() - t0) * 1e3
 
 
-def kernel_alone(B, H, L, S, encodings, launches):
-    """Milliseconds per aimet_attn_softmax launch on [B H, L, S], out of place, back to back."""
+def kernel_alone(B, H, L, S, encodings, launches, backward=False):
+    """Milliseconds per aimet_attn_softmax (or _backward) launch on [B H, L, S], out of place, back to back."""
     scores = torch.randn(B * H, L, S, device="cuda") * 3.0
     out = torch.empty_like(scores)
+    grad = torch.randn_like(scores) if backward else None
     s_enc, p_enc = ((-8.0, 127.0 / 16.0, 8), (0.0, 255.0 / 256.0, 8)) if encodings else (None, None)
 
     def run(n):
         for _ in range(n):
-            T.attn_softmax(scores, B, H, None, None, s_enc, p_enc, out=out)
+            if backward:
+                T.attn_softmax_backward(scores, grad, B, H, None, None, s_enc, p_enc, out=out)
+            else:
+                T.attn_softmax(scores, B, H, None, None, s_enc, p_enc, out=out)
     run(5)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
@@ -126,18 +134,53 @@ def main():
                      "launches per fused forward %d" % (name, r["max_abs_diff"], r["output_max_abs"],
                                                         r["launches_per_forward"]))
         m.fused = True
-        del sim, m, attn
+        # a training step in ACTIVE mode (the last compute_encodings left it there)
+        grad_out = torch.randn(L, B, E, device="cuda")
+
+        def train(fused_backward, model=m):
+            model.fused_backward = fused_backward
+            model.zero_grad(set_to_none=True)
+            xg = x.clone().requires_grad_(True)
+            model(xg, xg, xg, need_weights=False)[0].backward(grad_out)
+            return xg.grad
+        n0 = (T.attn_launch_count(), T.attn_backward_launch_count())
+        g_f = train(True)
+        r["launches_per_train_step"] = [T.attn_launch_count() - n0[0], T.attn_backward_launch_count() - n0[1]]
+        g_l = train(False)
+        r["train_grad_max_abs_diff"], r["train_grad_max_abs"] = float((g_f - g_l).abs().max()), float(g_l.abs().max())
+        del g_f, g_l
+        times, peak = {True: [], False: []}, {}
+        for _ in range(a.runs):
+            for fb in (True, False):
+                torch.cuda.reset_peak_memory_stats()
+                times[fb].append(timed(lambda: train(fb)))
+                peak[fb] = torch.cuda.max_memory_allocated()
+        r["train"] = {"fused": spread(times[True]), "literal": spread(times[False]),
+                      "literal_over_fused": statistics.median(times[False]) / statistics.median(times[True]),
+                      "fused_peak_bytes": peak[True], "literal_peak_bytes": peak[False]}
+        f, l = r["train"]["fused"], r["train"]["literal"]
+        lines.append("%-4s E %d H %d L=S %d B %d  %-8s fused %8.2f [%8.2f .. %8.2f]   literal %8.2f [%8.2f .. %8.2f]   "
+                     "literal / fused %.2f   peak memory fused %.0f MB, literal %.0f MB"
+                     % (name, E, H, L, B, "TRAIN", f["ms"], f["min"], f["max"], l["ms"], l["min"], l["max"],
+                        r["train"]["literal_over_fused"], peak[True] / 1e6, peak[False] / 1e6))
+        lines.append("%-4s largest input-gradient difference between the routes %.3g of %.3g; launches per fused "
+                     "training step: %d forward, %d backward" % (name, r["train_grad_max_abs_diff"],
+                                                                 r["train_grad_max_abs"], *r["launches_per_train_step"]))
+        m.fused_backward = False
+        del sim, m, attn, grad_out
         torch.cuda.empty_cache()
-        for encodings in (True, False):
-            ms = kernel_alone(B, H, L, L, encodings, a.kernel_launches)
-            bytes_moved = 8.0 * B * H * L * L
-            key = "kernel_both_encodings" if encodings else "kernel_no_encoding"
+        for backward, encodings in ((False, True), (False, False), (True, True), (True, False)):
+            ms = kernel_alone(B, H, L, L, encodings, a.kernel_launches, backward)
+            bytes_moved = (12.0 if backward else 8.0) * B * H * L * L
+            key = ("backward_" if backward else "") + ("kernel_both_encodings" if encodings else "kernel_no_encoding")
             r[key] = {"ms": ms, "bytes": bytes_moved, "bytes_per_s": bytes_moved / (ms * 1e-3),
                       "fraction_of_8TBs": bytes_moved / (ms * 1e-3) / HBM_BYTES_PER_S}
-            lines.append("%-4s aimet_attn_softmax alone on [%d, %d, %d], %s: %.3f ms per launch, %.0f MB read + written, "
-                         "%.2f TB/s = %.2f of 8 TB/s" % (name, B * H, L, L, "both encodings" if encodings else
-                                                         "no encoding", ms, bytes_moved / 1e6,
-                                                         r[key]["bytes_per_s"] / 1e12, r[key]["fraction_of_8TBs"]))
+            lines.append("%-4s %s alone on [%d, %d, %d], %s: %.3f ms per launch, %.0f MB read + written, "
+                         "%.2f TB/s = %.2f of 8 TB/s" % (name, "aimet_attn_softmax_backward" if backward else
+                                                         "aimet_attn_softmax", B * H, L, L,
+                                                         "both encodings" if encodings else "no encoding", ms,
+                                                         bytes_moved / 1e6, r[key]["bytes_per_s"] / 1e12,
+                                                         r[key]["fraction_of_8TBs"]))
         torch.cuda.empty_cache()
     text = "\n".join(lines) + "\n" + json.dumps(result, sort_keys=True) + "\n"
     sys.stdout.write(text)

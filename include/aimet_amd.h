@@ -1068,6 +1068,30 @@ int64_t aimet_attn_softmax_max_s(void);
 /* Kernel launches aimet_attn_softmax has issued in this process; reset != 0 zeroes it. */
 int aimet_attn_launch_count(int64_t* count, int reset);
 
+/* The straight-through gradient of aimet_attn_softmax for fixed encodings, in one launch: from the RAW
+ * scores the forward read and the gradient g at the quantized probabilities (both [B H, L, S] float32,
+ * contiguous), with the masks and encodings of the forward. Per row, in float32:
+ *   p_j  = e_j / s of the forward, recomputed by the same device functions in the same order: bit for
+ *          bit the forward's probability before its QDQ
+ *   G_j  = (pmin <= p_j <= pmax) ? g_j : 0              null prob_enc: G_j = g_j
+ *   d    = sum_j G_j p_j, every product rounded, in the order of s for this S
+ *   t_j  = (G_j - d) p_j
+ *   grad_scores_j = masked(j) ? 0 : ((smin <= scores_j <= smax) ? t_j : 0)     null score_enc: no range test
+ * smin, smax, pmin, pmax are the encodings' min / max rounded to float32 (the bounds
+ * aimet_ste_backward_per_tensor is given), not the grid's ends. A masked position is exactly 0, so a
+ * fully masked row (p = NaN) is all zeros. grad_scores may be grad_probs. S <= 1024: scores, grad_probs
+ * and grad_scores are touched once each; longer rows: grad_probs, scores and the masks are read a second
+ * time right after the first (csrc/attn_softmax.hip). Sizes, pointers and the S bound are checked as
+ * aimet_attn_softmax checks them; on an error nothing is written. */
+int aimet_attn_softmax_backward(const float* scores, const float* grad_probs, float* grad_scores, int64_t B, int64_t H,
+                                int64_t L, int64_t S, const uint8_t* attn_mask, int attn_mask_per_bh,
+                                const uint8_t* key_padding_mask, const aimet_tf_encoding* score_enc,
+                                const aimet_tf_encoding* prob_enc, void* stream);
+
+/* Kernel launches aimet_attn_softmax_backward has issued in this process (aimet_attn_launch_count
+ * counts forward launches only); reset != 0 zeroes it. */
+int aimet_attn_backward_launch_count(int64_t* count, int reset);
+
 /* ---- PEFT LoRA adapters in QuantSim (aimet_torch/peft.py LoraLayer) -------------------------------
  * The element-wise tail of an adapted layer, one launch each, equal bit for bit to the wrapped children
  * called one by one (csrc/lora.hip states every rounding). All tensors of a call hold n elements of one
