@@ -244,6 +244,8 @@ _PROTOTYPES = {
     "aimet_seqmse_candidate_qdq": [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp],
     "aimet_seqmse_recon_sums_workspace": [_i64, _i64, _i64, _i64, _i64p],
     "aimet_seqmse_recon_sums": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp],
+    "aimet_bq_seqmse_losses": [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _int, _int, _vp,
+                               _vp, _vp],
     "aimet_fp8_scale_table": [_vp, _i64, _int, _vp, _vp],
     "aimet_fp8_qdq": [_vp, _vp, _i64, _i64, _i64, _vp, _int, _vp],
     "aimet_fp8_search_workspace": [_i64, _i64, _i64, _i64p],

@@ -232,6 +232,26 @@ class BlockwiseQuantizer(StaticGridTensorQuantizer):
             self.use_unsigned_symmetric, self.scale_bitwidth, out)
         self._fused = (self._key(t), out)
 
+    def set_block_ranges(self, mins: torch.Tensor, maxs: torch.Tensor):
+        """Encodings from one chosen (min, max) range per block ([E] each, the table's order) instead
+        of the weight's own, then frozen: what a blockwise quantizer computes from
+        ``stack([x_min, x_max])`` (aimet_torch/v2/seq_mse.py compute_param_encodings). One
+        aimet_bq_encode_qdq launch on the [R][NB][2] tensor of pairs with the quantizer's symmetry flags
+        and scale bitwidth, so LPBQ compresses the chosen block scales by the calibration kernel's
+        arithmetic. The quantizer's own block length (the weight's) stays."""
+        if self._is_encoding_frozen:
+            raise RuntimeError("Encoding can be set only when it is not frozen.")
+        E = self.num_encodings
+        if tuple(mins.shape) != (E,) or tuple(maxs.shape) != (E,):
+            raise ValueError("expected %d block minima and maxima, got %s and %s"
+                             % (E, tuple(mins.shape), tuple(maxs.shape)))
+        pairs = torch.stack([mins.detach(), maxs.detach()], dim=-1).to(torch.float32).contiguous()
+        self.table, self.int_scale, self.channel_scale = encode_qdq(
+            pairs, self.R, self.NB, 2, self.bitwidth, self.use_symmetric_encodings, self.use_strict_symmetric,
+            self.use_unsigned_symmetric, self.scale_bitwidth)
+        self._pending = self._fused = None
+        self.freeze_encoding()
+
     @staticmethod
     def _key(t):
         return (t.data_ptr(), t._version, tuple(t.shape), t.dtype, t.device)

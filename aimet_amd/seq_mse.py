@@ -23,6 +23,15 @@ The candidates of one window are held at once: ``CANDIDATE_WINDOW_BYTES`` bounds
 stacked weights plus the stacked output of one batch (Llama-3-8B's lm_head at 20 candidates would be
 42 GB). ``checkpoints_config`` (block-wise sampling) is not implemented; calibration batches are
 cached in device memory.
+
+Blockwise and LPBQ weight quantizers (aimet_amd/blockwise.py) follow aimet_torch/v2/seq_mse.py: the
+candidates are per block of input features, the loss is taken per (output row, block) before the
+blocks' partial products are added, and the best candidate is chosen per block. For a Linear that
+is ONE launch per batch (``aimet_bq_seqmse_losses``, csrc/seqmse_block.hip: the candidates' QDQ,
+both products on the fp32 matrix cores and the loss sums, nothing stacked, no window); the
+candidates' tables come from the blockwise encoding kernel itself, so the frozen table is bit for
+bit the searched one. An LPBQ quantizer searches as plain blockwise and compresses the chosen
+block scales afterwards (``BlockwiseQuantizer.set_block_ranges``).
 """
 import contextlib
 import ctypes
@@ -34,12 +43,13 @@ import torch.nn.functional as functional
 
 from aimet_amd import _native
 from aimet_amd.activation_sampler import StopForwardException, _device_of, _to_device, default_forward_fn
+from aimet_amd.blockwise import BlockwiseQuantizer, encode_qdq
 from aimet_amd.libpymo import RoundingMode
 from aimet_amd.qc_quantize_op import QcQuantizeOpMode, QcQuantizeWrapper
 from aimet_amd.quantizers import (QuantScheme, StaticGridPerChannelQuantizer, StaticGridPerTensorQuantizer,
                                   StaticGridTensorQuantizer)
 from aimet_amd.quantsim import QuantizationSimModel, _eval_mode
-from aimet_amd.tensor_quantizer import _require_gpu, _stream
+from aimet_amd.tensor_quantizer import _require_gpu, _stream, qdq_per_channel_table
 
 # The following modules with weights are supported
 SUPPORTED_MODULES = (torch.nn.Linear, torch.nn.Conv2d)
@@ -148,6 +158,10 @@ class SequentialMse:
         _check_params(params)
         if sim._quant_scheme not in (QuantScheme.post_training_tf, QuantScheme.training_range_learning_with_tf_init):
             raise AssertionError("Use TF quant-scheme with sequential MSE.")
+
+        grouped = cls._get_grouped_convs_with_blockwise_quantization(model, sim)
+        if grouped:
+            modules_to_exclude = list(modules_to_exclude or []) + grouped
 
         with cls.temporarily_disable_quantizers(model, sim, modules_to_exclude):
             # Initialize param encodings of modules of supported types.
@@ -279,6 +293,22 @@ class SequentialMse:
                             quantizers_to_be_disabled.append(quantizer)
         return quantizers_to_be_disabled
 
+    @staticmethod
+    def _get_grouped_convs_with_blockwise_quantization(model: torch.nn.Module, sim: QuantizationSimModel
+                                                       ) -> List[torch.nn.Module]:
+        """The FP32 modules of the grouped convolutions whose weight quantizer is blockwise: the blocks
+        of a grouped weight do not line up with slices of the input, so they are left out of the search."""
+        # pylint: disable=protected-access
+        name_to_fp32_module_dict = dict(model.named_modules())
+        grouped = []
+        for name, quant_wrapper in sim.quant_wrappers():
+            module = quant_wrapper._module_to_wrap
+            if isinstance(module, torch.nn.Conv2d) and module.groups != 1 and \
+                    isinstance(quant_wrapper.param_quantizers.get('weight'), BlockwiseQuantizer) and \
+                    name in name_to_fp32_module_dict:
+                grouped.append(name_to_fp32_module_dict[name])
+        return grouped
+
     @classmethod
     @contextlib.contextmanager
     def temporarily_disable_quantizers(cls, model: torch.nn.Module, sim: QuantizationSimModel,
@@ -381,6 +411,9 @@ class SequentialMse:
         # pylint: disable=too-many-locals
         _check_params(params)
         quantizer = quant_module.param_quantizers['weight']
+        if isinstance(quantizer, BlockwiseQuantizer):
+            cls._optimize_blockwise_module(quant_module, x, xq, params)
+            return
         per_channel_min, per_channel_max = cls.get_per_channel_min_and_max(quant_module)
         candidates = cls.get_candidates(params.num_candidates, per_channel_max, per_channel_min)
 
@@ -453,6 +486,99 @@ class SequentialMse:
                 loss = cls.compute_recon_loss(xqwq, xw, params, channel_dim=1 if conv else -1)
                 total_loss[first:first + count] += loss.view(count, C)
             del wq, stacked
+        return total_loss
+
+    @classmethod
+    def get_min_and_max_for_candidate_selection(cls, quant_module: QcQuantizeWrapper
+                                                ) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+        """
+        Min/max per block of a blockwise weight quantizer, as [E] float32 tensors in the order of the
+        quantizer's table ([channel][block]); absmax and no min for a symmetric quantizer.
+
+        :param quant_module: Quant module to be optimized
+        :return: (block_min or None, block_max)
+        """
+        quantizer = quant_module.param_quantizers['weight']
+        weight = cls._get_original_module(quant_module).weight.detach().to(torch.float32)
+        blocks = weight.reshape(quantizer.num_encodings, quantizer.BL)
+        if cls._is_symmetric_quantizer(quantizer):
+            return None, blocks.abs().max(dim=1)[0]
+        return blocks.min(dim=1)[0], blocks.max(dim=1)[0]
+
+    @classmethod
+    def _optimize_blockwise_module(cls, quant_module: QcQuantizeWrapper, x: torch.Tensor, xq: torch.Tensor,
+                                   params: SeqMseParams):
+        """optimize_module for a BlockwiseQuantizer (plain or LPBQ): the best candidate per block."""
+        quantizer = quant_module.param_quantizers['weight']
+        block_min, block_max = cls.get_min_and_max_for_candidate_selection(quant_module)
+        candidates = cls.get_candidates(params.num_candidates, block_max, block_min)
+        with torch.no_grad():
+            tables = cls._block_candidate_tables(quantizer, candidates)
+            total_loss = cls._block_candidate_losses(quant_module, tables, x, xq, params)   # [n, R, NB]
+            best_indices = _first_argmin(total_loss.reshape(params.num_candidates, -1)).unsqueeze(0)
+            best_max = torch.stack([cand_max for cand_max, _ in candidates]).gather(0, best_indices)[0]
+            best_min = torch.stack([cand_min for _, cand_min in candidates]).gather(0, best_indices)[0]
+        quantizer.set_block_ranges(best_min, best_max)
+
+    @staticmethod
+    def _block_candidate_tables(quantizer: BlockwiseQuantizer, candidates) -> torch.Tensor:
+        """[n][4][E]: every candidate's table as the plain blockwise encoding kernel gives it for the
+        candidate's (min, max) pair per block -- one launch on the [n R][NB][2] tensor of pairs, the
+        arithmetic set_block_ranges freezes the choice with."""
+        n, E = len(candidates), quantizer.num_encodings
+        pairs = torch.stack([torch.stack([cand_min, cand_max], dim=-1) for cand_max, cand_min in candidates])
+        table, _, _ = encode_qdq(pairs.to(torch.float32).contiguous(), n * quantizer.R, quantizer.NB, 2,
+                                 quantizer.bitwidth, quantizer.use_symmetric_encodings, quantizer.use_strict_symmetric,
+                                 quantizer.use_unsigned_symmetric)
+        return table.view(4, n, E).permute(1, 0, 2).contiguous()
+
+    @classmethod
+    def _block_candidate_losses(cls, quant_module, tables, x, xq, params) -> torch.Tensor:
+        """total_loss [num_candidates, R, NB] of the reference's per-block candidate loop. A Linear is one
+        aimet_bq_seqmse_losses launch per batch. A Conv2d (groups == 1) runs the reference's loop
+        on what exists: per block a slice of x, xq, w and the candidates' QDQ'd w along the input
+        channels through compute_outputs and compute_recon_loss -- correct, not fast."""
+        # pylint: disable=too-many-locals
+        module = cls._get_original_module(quant_module)
+        quantizer = quant_module.param_quantizers['weight']
+        w = module.weight.detach().contiguous()
+        _require_gpu(w, what="weight", allow_16bit=True)
+        n_cand = int(params.num_candidates)
+        R, NB, BL, bs = quantizer.R, quantizer.NB, quantizer.BL, quantizer.block_size
+        kind = _LOSS_KINDS[params.loss_fn]
+        total_loss = torch.zeros((n_cand, R, NB), dtype=torch.float32, device=w.device)
+
+        if isinstance(module, torch.nn.Linear):
+            code = _native.io_code(w.dtype, TypeError, "Sequential MSE takes float32, float16 or bfloat16 weights "
+                                                       "(got %s)")
+            sig = torch.empty((R, NB), dtype=torch.float32, device=w.device) if params.loss_fn == "sqnr" else None
+            for batch_idx in range(params.num_batches):
+                xb = x[batch_idx].reshape(-1, NB * bs).to(w.dtype).contiguous()
+                same = xq is x
+                xqb = xb if same else xq[batch_idx].reshape(-1, NB * bs).to(w.dtype).contiguous()
+                T = xb.shape[0]
+                err = torch.empty((n_cand, R, NB), dtype=torch.float32, device=w.device)
+                with torch.cuda.device(w.device):
+                    _native.call("aimet_bq_seqmse_losses", xb.data_ptr(), xqb.data_ptr(), NB * bs, w.data_ptr(), T,
+                                 R, NB, bs, tables.data_ptr(), n_cand, 0, n_cand, kind, code, err.data_ptr(),
+                                 sig.data_ptr() if sig is not None else None, _stream(w))
+                if sig is None:
+                    total_loss += err
+                else:   # neg_sqnr from the sums, per batch
+                    total_loss += -10 * torch.log10((sig / float(T)).unsqueeze(0) / (err / float(T) + _SQNR_EPS))
+            return total_loss
+
+        if not isinstance(module, torch.nn.Conv2d) or module.groups != 1:
+            raise ValueError('Unsupported module: ', module)
+        w32 = w.to(torch.float32)
+        wq = torch.stack([qdq_per_channel_table(w32, tables[j], 1, R * NB, BL, RoundingMode.ROUND_NEAREST)
+                          for j in range(n_cand)]).to(w.dtype).reshape((n_cand * R,) + tuple(w.shape[1:]))
+        for b in range(NB):
+            cols = slice(b * bs, (b + 1) * bs)
+            w_b, wq_b = w[:, cols].contiguous(), wq[:, cols].contiguous()
+            for batch_idx in range(params.num_batches):
+                xqwq, xw = cls.compute_outputs(quant_module, x[batch_idx][:, cols], xq[batch_idx][:, cols], w_b, wq_b)
+                total_loss[:, :, b] += cls.compute_recon_loss(xqwq, xw, params, channel_dim=1).view(n_cand, R)
         return total_loss
 
     @staticmethod

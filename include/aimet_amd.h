@@ -719,6 +719,21 @@ int aimet_seqmse_recon_sums(const float* xw, const float* xqwq, int64_t outer, i
                             int64_t count, int loss_kind, float* err, float* sig, void* workspace,
                             int64_t workspace_bytes, void* stream);
 
+/* aimet_torch/v2/seq_mse.py _compute_loss with a block size, for a Linear layer and the candidates
+ * [first, first + count) in one launch. x, xq [T][NB * BS] with row stride ld (elements; they may be
+ * the same pointer), w [R][NB * BS] contiguous, all of io_dtype (0 float32, 1 float16, 2 bfloat16);
+ * tables_dev [num_candidates][4][E] as aimet_seqmse_candidate_tables writes them at C = E = R * NB
+ * ([row][block] order). err [count][R][NB] (float32) = sum over t of d^2 (MSE, SQNR) or |d| (L1),
+ *   d = sum_k xq[t][b BS + k] wq_c[r][b BS + k] - sum_k x[t][b BS + k] w[r][b BS + k],
+ * wq_c the nearest-rounding QDQ of w with column r * NB + b of candidate c's table (rounded once to
+ * a 16-bit io_dtype); for SQNR also sig [R][NB] = sum over t of (sum_k x w)^2 (sig may be NULL
+ * otherwise). Both products are formed on the fp32 matrix cores and subtracted, whether or not x
+ * and xq alias. The candidate weights and the outputs stay on chip; no workspace, no atomics, equal
+ * inputs give equal bits. BS a multiple of 4 from 4 to 256. */
+int aimet_bq_seqmse_losses(const void* x, const void* xq, int64_t ld, const void* w, int64_t T, int64_t R,
+                              int64_t NB, int64_t BS, const float* tables_dev, int64_t num_candidates, int64_t first,
+                              int64_t count, int loss_kind, int io_dtype, float* err, float* sig, void* stream);
+
 /* ---- FP8 fake-quantization (aimet_torch/fp_quantization.py) -------------------------------------
  * mantissa_bits M in 1..6, E = 7 - M exponent bits, subnormals, no NaN / Inf code, the bias set by
  * maxval. F = (2 - 2^-M) * 2^(2^E - 1), alpha = float32(double(maxval) / F); per element
