@@ -113,6 +113,15 @@ class BnreFoldScaleJobC(ctypes.Structure):
     _fields_ = [("fold", DfqBnFoldJobC), ("enc_min", ctypes.c_void_p), ("enc_max", ctypes.c_void_p)]
 
 
+class AttnLgGridC(ctypes.Structure):
+    """aimet_attn_lg_grid."""
+    _fields_ = [("encoding_min", ctypes.c_void_p), ("encoding_max", ctypes.c_void_p), ("bitwidth", ctypes.c_int),
+                ("use_symmetric", ctypes.c_int), ("use_strict_symmetric", ctypes.c_int),
+                ("is_unsigned_symmetric", ctypes.c_int)]
+
+
+_lg_grid_p = ctypes.POINTER(AttnLgGridC)
+
 # name -> argtypes (restype is int status unless listed in _RESTYPES)
 _PROTOTYPES = {
     "aimet_last_error": [],
@@ -283,6 +292,10 @@ _PROTOTYPES = {
     "aimet_attn_launch_count": [_i64p, _int],
     "aimet_attn_softmax_backward": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _vp, _enc_p, _enc_p, _vp],
     "aimet_attn_backward_launch_count": [_i64p, _int],
+    "aimet_attn_softmax_lg": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _vp, _lg_grid_p, _vp, _lg_grid_p, _vp, _vp],
+    "aimet_attn_softmax_lg_backward": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _vp, _lg_grid_p, _vp, _vp,
+                                       _lg_grid_p, _vp, _vp, _vp],
+    "aimet_attn_lg_launch_count": [_i64p, _i64p, _int],
     "aimet_lora_merge": [_vp, _vp, _vp, _i64, _int, _enc_p, _enc_p, _enc_p, _vp],
     "aimet_lora_merge_backward": [_vp, _vp, _vp, _vp, _vp, _i64, _int, _enc_p, _enc_p, _enc_p, _vp],
     "aimet_lora_scale": [_vp, _vp, _i64, _int, ctypes.c_float, _enc_p, _enc_p, _vp],

@@ -60,9 +60,34 @@
 //     same workgroup, so they are expected from L2 (12 B an element from HBM; not confirmed by a counter run).
 //   grad_scores may be grad_probs (or scores) itself: on the wave path the row is in registers before
 //   the first store; in pass T a thread reads exactly the elements it then writes.
+//
+// Range learning (aimet_attn_softmax_lg, aimet_attn_softmax_lg_backward): the same rows with both
+// quantizers on learned grids, the element arithmetic of lg_core.hpp (calculate_forward_pass,
+// asymmetric_gradients / symmetric_gradients; round half to even). wave_row_exp and lds_row_exp are
+// templates over their argument record and find score_of by overload: Args gives the static kernels
+// what they were, LgRowArgs the learned grid.
+//   Forward: a quantizer's trainable range arrives as two device pointers; every thread computes delta and
+//     offset with LgEnc::of, x_j = lg_qdq(scores_j), then masks, m, e_j, s, p_j as above, probs_j =
+//     lg_qdq(p_j). One thread stores each quantizer's {delta, offset, min, max} for the backward. The
+//     host reads nothing back. Out of place.
+//   Backward, per element that is not masked (a masked one gets exactly 0 and adds to no sum):
+//     q = p_j / delta_p (lg_quot), m_p its in-grid mask: G_j = m_p g_j, and the probability quantizer's
+//       {A, B, D} terms of lg_bwd_term_m with gradient g_j
+//     d = sum_j G_j p_j in the ORDER ABOVE, t_j = (G_j - d) p_j
+//     q = scores_j / delta_s, m_s: dx_j = m_s t_j, and the score quantizer's {A, B, D} terms with gradient t_j
+//   A lane carries its six sums over the rows of its grid-stride loop (rows in increasing index, a
+//   row's elements in increasing j); block_fold_own makes the workgroup's partial. The partials go to a
+//   scratch block and a SECOND LAUNCH of one workgroup folds them -- lane l adds partials l, l + 256, ...
+//   in increasing index, then the same tree -- and applies range_grads_one on the saved range of each
+//   quantizer. (The per-tensor learned-grid backward folds the same way; its fold in the last workgroup
+//   to arrive measured slower than the launch, learned_grid.hip.) No atomics: equal inputs, equal bits.
+//   Wave path: g, p and the raw score in registers (3 NI values a lane) and NI live bits. LDS path: p in
+//   LDS and g read again as above; pass T keeps pass D's thread-to-element map with dword accesses, so
+//   the order of every sum is independent of the row's alignment.
 
 #include "common.hpp"
 #include "io16.hpp"
+#include "lg_core.hpp"
 #include "reduce.hpp"
 #include "rnn_math.hpp"
 
@@ -146,6 +171,32 @@ __device__ __forceinline__ float score_of(const Args& a, const Row& w, float x, 
     return x;
 }
 
+// Range learning: one quantizer's grid as a kernel holds it. delta and offset come from the device --
+// LgEnc::of on the trainable range in the forward, the forward's four saved floats in the backward.
+struct LgGrid
+{
+    float d, o, steps, rd;   // rd = lg_recip(d)
+    int on;                  // 0: no quantizer
+    int mode;                // lg_bwd_term's: 1 symmetric_gradients, 2 asymmetric_gradients
+};
+
+// what the row functions below read of their `a` on the range-learning kernels
+struct LgRowArgs
+{
+    int S;
+    LgGrid sq;
+};
+
+// steps 1 and 2 on a learned grid (calculate_forward_pass: round half to even)
+__device__ __forceinline__ float score_of(const LgRowArgs& a, const Row& w, float x, int j, float)
+{
+    if (a.sq.on)
+        x = lg_qdq(x, a.sq.d, a.sq.o, a.sq.steps, a.sq.rd);
+    if (masked_at(w, j))
+        x = neg_inf();
+    return x;
+}
+
 __device__ __forceinline__ float exp_of(float x, float m)
 {
     return x == neg_inf() ? 0.0f : rnn_math::exp_r(x - m);
@@ -188,8 +239,8 @@ __device__ __forceinline__ float wave_sum(float v)
 // ---- wave path: NI values a lane ---------------------------------------------------------------
 // Lane `lane`'s NI values of row w into x as e_j (an element past S: 0); returns s. raw(i, j, score)
 // sees every raw score the lane loads.
-template <int NI, class Raw>
-__device__ __forceinline__ float wave_row_exp(const Args& a, const Row& w, int lane, float s_rcp, float (&x)[NI],
+template <int NI, class A, class Raw>
+__device__ __forceinline__ float wave_row_exp(const A& a, const Row& w, int lane, float s_rcp, float (&x)[NI],
                                               Raw raw)
 {
     const int S = a.S;
@@ -293,7 +344,8 @@ __global__ __launch_bounds__(kBlk) void attn_softmax_bwd_wave(const Args a)
 // ---- LDS path ----------------------------------------------------------------------------------
 // Row w into `row` as e_j; returns s. `red` holds four floats; the caller puts a barrier between its
 // last read of row / red and the next call.
-__device__ __forceinline__ float lds_row_exp(const Args& a, const Row& w, float* row, float* red, float s_rcp)
+template <class A>
+__device__ __forceinline__ float lds_row_exp(const A& a, const Row& w, float* row, float* red, float s_rcp)
 {
     const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
     const int S = a.S;
@@ -457,6 +509,301 @@ __global__ __launch_bounds__(kBlk) void attn_softmax_bwd_lds(const Args a)
     }
 }
 
+// ---- range learning: aimet_attn_softmax_lg / aimet_attn_softmax_lg_backward ---------------------------
+// The same rows on learned grids (header comment, "Range learning"). Both kernels of a pair take
+// LgArgs: the tensors, masks and shape in `a` (its static-grid fields unused) and one LgEnc a
+// quantizer, emin == nullptr where there is none; delta_out / offset_out / range_out are the four
+// saved floats {delta, offset, min, max} -- written by the forward, read by the backward.
+struct LgArgs
+{
+    Args a;
+    LgEnc se, pe;
+    float* partial;   // backward: six sums a workgroup
+};
+
+// forward: the grid from the trainable range as it stands on the device; one thread of the launch
+// saves it for the backward
+__device__ __forceinline__ LgGrid grid_of_range(const LgEnc& e, bool save)
+{
+    LgGrid g {1.0f, 0.0f, 0.0f, 1.0f, 0, 0};
+    if (e.emin == nullptr)
+        return g;
+    const float mn = e.emin[0], mx = e.emax[0];
+    e.of(mn, mx, g.d, g.o);
+    if (save)
+    {
+        e.delta_out[0]  = g.d;
+        e.offset_out[0] = g.o;
+        e.range_out[0]  = mn;
+        e.range_out[1]  = mx;
+    }
+    g.steps = e.steps, g.rd = lg_recip(g.d), g.on = 1, g.mode = e.mode == 2 ? 2 : 1;
+    return g;
+}
+
+// backward: the grid the forward saved
+__device__ __forceinline__ LgGrid grid_saved(const LgEnc& e)
+{
+    LgGrid g {1.0f, 0.0f, 0.0f, 1.0f, 0, 0};
+    if (e.emin == nullptr)
+        return g;
+    g.d = e.delta_out[0], g.o = e.offset_out[0];
+    g.steps = e.steps, g.rd = lg_recip(g.d), g.on = 1, g.mode = e.mode == 2 ? 2 : 1;
+    return g;
+}
+
+__device__ __forceinline__ float lg_prob_of(const LgGrid& pq, float e, float s)
+{
+    const float p = unq_prob(e, s);
+    return pq.on ? lg_qdq(p, pq.d, pq.o, pq.steps, pq.rd) : p;
+}
+
+template <int NI>
+__global__ __launch_bounds__(kBlk) void attn_softmax_lg_wave(const LgArgs k)
+{
+    const int lane  = threadIdx.x & (kWave - 1);
+    const int wave  = threadIdx.x / kWave;
+    const int S     = k.a.S;
+    const bool save = blockIdx.x == 0 && threadIdx.x == 0;
+    const LgRowArgs a {S, grid_of_range(k.se, save)};
+    const LgGrid pq = grid_of_range(k.pe, save);
+    constexpr int kRows = kBlk / kWave;
+    for (int64_t r = (int64_t) blockIdx.x * kRows + wave; r < k.a.rows; r += (int64_t) gridDim.x * kRows)
+    {
+        const Row w = row_of(k.a, r);
+        float x[NI];
+        const float s = wave_row_exp<NI>(a, w, lane, 0.0f, x, [](int, int, float) {});
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+        {
+            const int j = lane + i * kWave;
+            if (j < S)
+                w.dst[j] = lg_prob_of(pq, x[i], s);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlk) void attn_softmax_lg_lds(const LgArgs k)
+{
+    extern __shared__ float4 lds4[];
+    float* row = reinterpret_cast<float*>(lds4);   // S floats
+    float* red = row + ((k.a.S + 3) & ~3);         // 4 floats
+    const int t = threadIdx.x;
+    const int S = k.a.S;
+    const bool save = blockIdx.x == 0 && t == 0;
+    const LgRowArgs a {S, grid_of_range(k.se, save)};
+    const LgGrid pq = grid_of_range(k.pe, save);
+    for (int64_t r = blockIdx.x; r < k.a.rows; r += gridDim.x)
+    {
+        const Row w   = row_of(k.a, r);
+        const float s = lds_row_exp(a, w, row, red, 0.0f);
+        // pass C: divide, quantize, store (attn_softmax_lds's, on the learned grid)
+        const int head = head_of(w.dst, S);
+        const int nvec = (S - head) >> 2;
+        const int tail = head + 4 * nvec;
+        for (int j = t; j < head; j += kBlk)
+            w.dst[j] = lg_prob_of(pq, row[j], s);
+        for (int v = t; v < nvec; v += kBlk)
+        {
+            const int j = head + 4 * v;
+            F4 f;
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                f.v[c] = lg_prob_of(pq, row[j + c], s);
+            *reinterpret_cast<F4*>(__builtin_assume_aligned(w.dst + j, 16)) = f;
+        }
+        for (int j = tail + t; j < S; j += kBlk)
+            w.dst[j] = lg_prob_of(pq, row[j], s);
+        __syncthreads();   // row and red are read out before the next row overwrites them
+    }
+}
+
+// The backward's six sums: {A, B, D} of lg_bwd_term_m for the score quantizer and for the probability
+// quantizer. A lane carries its own across the rows of its grid-stride loop.
+struct LgSums
+{
+    Sums s, p;
+};
+
+__device__ __forceinline__ LgSums add_sums(LgSums x, const LgSums& y)
+{
+    x.s.a += y.s.a, x.s.b += y.s.b, x.s.d += y.s.d;
+    x.p.a += y.p.a, x.p.b += y.p.b, x.p.d += y.p.d;
+    return x;
+}
+
+// x / delta as lg_bwd_elem forms it
+__device__ __forceinline__ float lg_quotient(const LgGrid& q, float x)
+{
+    return lg_fast_enc(q.o, q.rd) ? lg_quot(x, q.d, q.rd) : x / q.d;
+}
+
+// lg_grad's result alone (in-grid mask * g, lg_bwd_term_m's expressions), for a pass whose terms are
+// already in the sums
+__device__ __forceinline__ float lg_masked_grad(const LgGrid& q, float x, float g)
+{
+    if (!q.on)
+        return g;
+    const float xr = __builtin_rintf(lg_quotient(q, x)) - q.o;
+    return (__builtin_amdgcn_fmed3f(xr, 0.0f, q.steps) == xr ? 1.0f : 0.0f) * g;
+}
+
+// One quantizer's backward at x for the gradient g arriving at its output: the gradient passed on
+// (in-grid mask * g) and the element's terms added to t. No quantizer: g, nothing added.
+__device__ __forceinline__ float lg_grad(const LgGrid& q, float x, float g, Sums& t)
+{
+    if (!q.on)
+        return g;
+    const float qt = lg_quotient(q, x);
+    // Both modes' terms of the element (they share the quotient, the rounding and the mask), then one
+    // select a sum: 0 + term is the term, so the sums are those of lg_bwd_term adding in place. With
+    // the mode known only at run time, lg_bwd_term's branches were merged by the compiler into one add
+    // at a computed address, which put the running sums in private memory.
+    Sums sym {0.0f, 0.0f, 0.0f}, asym {0.0f, 0.0f, 0.0f};
+    float gx;
+    lg_bwd_term_m<1>(x, qt, g, q.o, q.steps, gx, sym);
+    lg_bwd_term_m<2>(x, qt, g, q.o, q.steps, gx, asym);
+    const bool two = q.mode == 2;
+    t.a += two ? asym.a : sym.a;
+    t.b += two ? asym.b : sym.b;
+    t.d += two ? asym.d : sym.d;
+    return gx;
+}
+
+// the workgroup's six sums (wave butterfly, then thread 0 folds waves 1..3) as its partial
+__device__ __forceinline__ void publish_sums(const LgSums& acc, LgSums* fold, float* partial)
+{
+    const LgSums t = block_fold_own<kBlk / kWave>(acc, fold, add_sums);
+    if (threadIdx.x == 0)
+    {
+        float* p = partial + 6 * (size_t) blockIdx.x;
+        p[0] = t.s.a, p[1] = t.s.b, p[2] = t.s.d;
+        p[3] = t.p.a, p[4] = t.p.b, p[5] = t.p.d;
+    }
+}
+
+template <int NI>
+__global__ __launch_bounds__(kBlk) void attn_softmax_lg_bwd_wave(const LgArgs k)
+{
+    __shared__ LgSums fold[kBlk / kWave];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    const int S    = k.a.S;
+    const LgRowArgs a {S, grid_saved(k.se)};
+    const LgGrid pq = grid_saved(k.pe);
+    Sums accs {0.0f, 0.0f, 0.0f}, accp {0.0f, 0.0f, 0.0f};   // this lane's, over all its rows
+    constexpr int kRows = kBlk / kWave;
+    for (int64_t r = (int64_t) blockIdx.x * kRows + wave; r < k.a.rows; r += (int64_t) gridDim.x * kRows)
+    {
+        const Row w = row_of(k.a, r);
+        float g[NI], p[NI], xr[NI];
+#pragma unroll
+        for (int i = 0; i < NI; ++i)   // in flight together with the scores
+        {
+            const int j = lane + i * kWave;
+            g[i]        = j < S ? w.g[j] : 0.0f;
+            xr[i]       = 0.0f;
+        }
+        unsigned live = 0;   // bit i: element i exists and is not masked
+        const float s = wave_row_exp<NI>(a, w, lane, 0.0f, p, [&](int i, int j, float x) {
+            xr[i] = x;
+            live |= (unsigned) !masked_at(w, j) << i;
+        });
+        float dacc = 0.0f;
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+        {
+            p[i]           = unq_prob(p[i], s);
+            g[i]           = (live >> i & 1u) ? lg_grad(pq, p[i], g[i], accp) : 0.0f;   // G_j
+            const float gp = g[i] * p[i];   // masked or past S: 0 * 0 (NaN in a fully masked row, which writes zeros)
+            dacc           = i == 0 ? gp : dacc + gp;
+        }
+        const float d = wave_sum(dacc);
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+        {
+            const int j = lane + i * kWave;
+            if (j < S)
+                w.dst[j] = (live >> i & 1u) ? lg_grad(a.sq, xr[i], (g[i] - d) * p[i], accs) : 0.0f;
+        }
+    }
+    if (k.partial)   // null: neither quantizer is present, nothing to fold
+        publish_sums(LgSums {accs, accp}, fold, k.partial);
+}
+
+// LDS path: p in LDS and g read again, as attn_softmax_bwd_lds; pass T keeps pass D's thread-to-element
+// map (dword t of each 256-dword group, loads and stores), so every element's terms are added by the
+// same lane in the same order whatever the row's alignment, and a thread reads exactly what it writes.
+__global__ __launch_bounds__(kBlk) void attn_softmax_lg_bwd_lds(const LgArgs k)
+{
+    extern __shared__ float4 lds4[];
+    float* row = reinterpret_cast<float*>(lds4);   // S floats
+    float* red = row + ((k.a.S + 3) & ~3);         // 4 floats
+    const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
+    const int S = k.a.S;
+    const LgRowArgs a {S, grid_saved(k.se)};
+    const LgGrid pq = grid_saved(k.pe);
+    Sums accs {0.0f, 0.0f, 0.0f}, accp {0.0f, 0.0f, 0.0f};   // this thread's, over all its rows
+    for (int64_t r = blockIdx.x; r < k.a.rows; r += gridDim.x)
+    {
+        const Row w   = row_of(k.a, r);
+        const float s = lds_row_exp(a, w, row, red, 0.0f);
+        __syncthreads();   // every thread has its s before red takes the partial sums of d
+        // pass D: p into LDS, the probability quantizer's terms, and d in the order of s
+        float dacc = 0.0f;
+        for (int j = t; j < S; j += kBlk)
+        {
+            const float p  = unq_prob(row[j], s);
+            row[j]         = p;
+            const float G  = masked_at(w, j) ? 0.0f : lg_grad(pq, p, w.g[j], accp);
+            const float gp = G * p;
+            dacc           = j == t ? gp : dacc + gp;
+        }
+        dacc = wave_sum(dacc);
+        if (lane == 0)
+            red[wave] = dacc;
+        __syncthreads();   // p and the four partial sums are in LDS
+        const float d = (red[0] + red[1]) + (red[2] + red[3]);
+        // pass T: G_j once more (its terms are pass D's), the score quantizer's terms, dx
+        for (int j = t; j < S; j += kBlk)
+        {
+            float dx = 0.0f;
+            if (!masked_at(w, j))
+            {
+                const float p = row[j];
+                const float G = lg_masked_grad(pq, p, w.g[j]);
+                dx            = lg_grad(a.sq, w.src[j], (G - d) * p, accs);
+            }
+            w.dst[j] = dx;
+        }
+        __syncthreads();   // row and red are read out before the next row overwrites them
+    }
+    if (k.partial)
+        publish_sums(LgSums {accs, accp}, reinterpret_cast<LgSums*>(row), k.partial);   // the row is free: S > 1024 floats
+}
+
+// The backward's second launch, one workgroup: lane l adds the partials l, l + 256, ... in increasing
+// index, then publish_sums' tree; thread 0 turns the six sums into the four range gradients.
+__global__ __launch_bounds__(kBlk) void attn_lg_fold(const float* __restrict__ partial, unsigned nparts, LgRange rs,
+                                                     LgRange rp)
+{
+    __shared__ LgSums fold[kBlk / kWave];
+    LgSums acc {};
+    for (unsigned i = threadIdx.x; i < nparts; i += kBlk)
+    {
+        const float* p = partial + 6 * (size_t) i;
+        acc            = add_sums(acc, LgSums {{p[0], p[1], p[2]}, {p[3], p[4], p[5]}});
+    }
+    const LgSums t = block_fold_own<kBlk / kWave>(acc, fold, add_sums);
+    if (threadIdx.x == 0)
+    {
+        if (rs.gmin)
+            range_grads_one(t.s.a, t.s.b, t.s.d, 0, rs);
+        if (rp.gmin)
+            range_grads_one(t.p.a, t.p.b, t.p.d, 0, rp);
+    }
+}
+
 bool aligned4(const void* p)
 {
     return (reinterpret_cast<uintptr_t>(p) & 3) == 0;
@@ -491,29 +838,60 @@ Args checked_args(const float* scores, int64_t B, int64_t H, int64_t L, int64_t 
     return a;
 }
 
-using Kernel = void (*)(Args);
+template <class KA>
+using Kernel = void (*)(KA);
 
-// wave[k] holds 2^k values a lane
-void launch_rows(const Args& a, const Kernel (&wave)[5], Kernel lds, hipStream_t s)
+// the workgroups launch_rows starts for this shape
+unsigned row_grid(const Args& a)
 {
+    return (unsigned) std::min<int64_t>(a.S <= kWaveMaxS ? ceil_div(a.rows, kBlk / kWave) : a.rows, kMaxGrid);
+}
+
+// wave[k] holds 2^k values a lane; ka: the kernels' argument, a: the shape in it
+template <class KA>
+void launch_rows(const KA& ka, const Args& a, const Kernel<KA> (&wave)[5], Kernel<KA> lds, hipStream_t s)
+{
+    const unsigned grid = row_grid(a);
     if (a.S <= kWaveMaxS)
     {
-        const unsigned grid = (unsigned) std::min<int64_t>(ceil_div(a.rows, kBlk / kWave), kMaxGrid);
-        int k               = 0;
+        int k = 0;
         while ((kWave << k) < a.S)
             ++k;
-        wave[k]<<<grid, kBlk, 0, s>>>(a);
+        wave[k]<<<grid, kBlk, 0, s>>>(ka);
     }
     else
     {
-        const unsigned grid = (unsigned) std::min<int64_t>(a.rows, kMaxGrid);
-        const size_t bytes  = (size_t) ((a.S + 3) & ~3) * 4 + 16;
-        lds<<<grid, kBlk, bytes, s>>>(a);
+        const size_t bytes = (size_t) ((a.S + 3) & ~3) * 4 + 16;
+        lds<<<grid, kBlk, bytes, s>>>(ka);
     }
     AIMET_LAUNCH_CHECK();
 }
 
 LaunchCounter g_backward_launches;
+LaunchCounter g_lg_launches, g_lg_backward_launches;
+
+// One quantizer of the range-learning entries as the kernels take it. forward: the grid from the
+// trainable range, `saved` written; backward: the range pointers of `grid` are not read, the encoding
+// is the saved one (LgEnc's pointers are not const: the forward writes through them).
+LgEnc lg_enc_of(const aimet_attn_lg_grid* grid, const float* saved, bool forward)
+{
+    if (grid == nullptr)
+        return LgEnc {};
+    require_device_ptr(saved, "saved encoding");
+    float* sv = const_cast<float*>(saved);
+    return enc_of(forward ? grid->encoding_min : sv + 2, forward ? grid->encoding_max : sv + 3, 1, 0, grid->bitwidth,
+                  grid->use_symmetric, grid->use_strict_symmetric, grid->is_unsigned_symmetric, sv, sv + 1, sv + 2);
+}
+
+// the range gradients of one quantizer from its saved encoding: range_grad[0] = min's, [1] = max's
+LgRange lg_range_of(const LgEnc& e, float* range_grad)
+{
+    if (e.emin == nullptr)
+        return LgRange {};
+    require_device_ptr(range_grad, "range gradient");
+    return LgRange {e.range_out, e.range_out + 1, e.delta_out, range_grad, range_grad + 1, e.steps, e.half_floor,
+                    e.mode != 2};
+}
 
 }   // namespace
 }   // namespace aimet_amd
@@ -531,8 +909,8 @@ int aimet_attn_softmax(const float* scores, float* probs, int64_t B, int64_t H, 
         require_device_ptr(probs, "attention probabilities");
         AIMET_REQUIRE(aligned4(scores) && aligned4(probs), "attention softmax: misaligned pointer");
         a.probs = probs;
-        launch_rows(a, {attn_softmax_wave<1>, attn_softmax_wave<2>, attn_softmax_wave<4>, attn_softmax_wave<8>,
-                        attn_softmax_wave<16>}, attn_softmax_lds, as_stream(stream));
+        launch_rows<Args>(a, a, {attn_softmax_wave<1>, attn_softmax_wave<2>, attn_softmax_wave<4>,
+                                 attn_softmax_wave<8>, attn_softmax_wave<16>}, attn_softmax_lds, as_stream(stream));
         g_launches.add(1);
     });
 }
@@ -549,9 +927,76 @@ int aimet_attn_softmax_backward(const float* scores, const float* grad_probs, fl
         AIMET_REQUIRE(aligned4(scores) && aligned4(grad_probs) && aligned4(grad_scores),
                       "attention softmax: misaligned pointer");
         a.grad = grad_probs, a.probs = grad_scores;
-        launch_rows(a, {attn_softmax_bwd_wave<1>, attn_softmax_bwd_wave<2>, attn_softmax_bwd_wave<4>,
-                        attn_softmax_bwd_wave<8>, attn_softmax_bwd_wave<16>}, attn_softmax_bwd_lds, as_stream(stream));
+        launch_rows<Args>(a, a, {attn_softmax_bwd_wave<1>, attn_softmax_bwd_wave<2>, attn_softmax_bwd_wave<4>,
+                                 attn_softmax_bwd_wave<8>, attn_softmax_bwd_wave<16>}, attn_softmax_bwd_lds,
+                          as_stream(stream));
         g_backward_launches.add(1);
+    });
+}
+
+int aimet_attn_softmax_lg(const float* scores, float* probs, int64_t B, int64_t H, int64_t L, int64_t S,
+                          const uint8_t* attn_mask, int attn_mask_per_bh, const uint8_t* key_padding_mask,
+                          const aimet_attn_lg_grid* score_grid, float* score_saved, const aimet_attn_lg_grid* prob_grid,
+                          float* prob_saved, void* stream)
+{
+    return guarded([&] {
+        LgArgs k {};
+        k.a = checked_args(scores, B, H, L, S, attn_mask, attn_mask_per_bh, key_padding_mask, nullptr, nullptr);
+        require_device_ptr(probs, "attention probabilities");
+        AIMET_REQUIRE(aligned4(scores) && aligned4(probs), "attention softmax: misaligned pointer");
+        AIMET_REQUIRE(probs != scores, "attention softmax on learned grids is out of place: the backward reads the "
+                                       "raw scores");
+        k.a.probs = probs;
+        k.se      = lg_enc_of(score_grid, score_saved, true);
+        k.pe      = lg_enc_of(prob_grid, prob_saved, true);
+        launch_rows<LgArgs>(k, k.a, {attn_softmax_lg_wave<1>, attn_softmax_lg_wave<2>, attn_softmax_lg_wave<4>,
+                                     attn_softmax_lg_wave<8>, attn_softmax_lg_wave<16>}, attn_softmax_lg_lds,
+                            as_stream(stream));
+        g_lg_launches.add(1);
+    });
+}
+
+int aimet_attn_softmax_lg_backward(const float* scores, const float* grad_probs, float* grad_scores, int64_t B,
+                                   int64_t H, int64_t L, int64_t S, const uint8_t* attn_mask, int attn_mask_per_bh,
+                                   const uint8_t* key_padding_mask, const aimet_attn_lg_grid* score_grid,
+                                   const float* score_saved, float* score_range_grad,
+                                   const aimet_attn_lg_grid* prob_grid, const float* prob_saved, float* prob_range_grad,
+                                   void* stream)
+{
+    return guarded([&] {
+        LgArgs k {};
+        k.a = checked_args(scores, B, H, L, S, attn_mask, attn_mask_per_bh, key_padding_mask, nullptr, nullptr);
+        require_device_ptr(grad_probs, "gradient of the attention probabilities");
+        require_device_ptr(grad_scores, "gradient of the attention scores");
+        AIMET_REQUIRE(aligned4(scores) && aligned4(grad_probs) && aligned4(grad_scores),
+                      "attention softmax: misaligned pointer");
+        k.a.grad = grad_probs, k.a.probs = grad_scores;
+        k.se = lg_enc_of(score_grid, score_saved, false);
+        k.pe = lg_enc_of(prob_grid, prob_saved, false);
+        const LgRange rs = lg_range_of(k.se, score_range_grad), rp = lg_range_of(k.pe, prob_range_grad);
+        hipStream_t s    = as_stream(stream);
+        const unsigned grid = row_grid(k.a);
+        Scratch<float> partial;   // stays empty where neither quantizer is present
+        if (rs.gmin || rp.gmin)
+            partial = Scratch<float>((size_t) 6 * grid, s);
+        k.partial = partial.get();
+        launch_rows<LgArgs>(k, k.a, {attn_softmax_lg_bwd_wave<1>, attn_softmax_lg_bwd_wave<2>,
+                                     attn_softmax_lg_bwd_wave<4>, attn_softmax_lg_bwd_wave<8>,
+                                     attn_softmax_lg_bwd_wave<16>}, attn_softmax_lg_bwd_lds, s);
+        g_lg_backward_launches.add(1);
+        if (partial)
+        {
+            attn_lg_fold<<<1, kBlk, 0, s>>>(partial.get(), grid, rs, rp);
+            AIMET_LAUNCH_CHECK();
+        }
+    });
+}
+
+int aimet_attn_lg_launch_count(int64_t* forward, int64_t* backward, int reset)
+{
+    return guarded([&] {
+        g_lg_launches.read(forward, reset);
+        g_lg_backward_launches.read(backward, reset);
     });
 }
 

@@ -875,6 +875,32 @@ class LearnedGridQuantWrapper(QcQuantizeWrapper):
             outputs.append(inner(t, index))
         return outputs
 
+    # -- a caller that computes the wrapped module's output itself (aimet_amd.transformers) ----------
+    def output_fusable(self) -> bool:
+        """StaticGridQuantWrapper.output_fusable for range learning: True when a caller may replace
+        this wrapper's forward by a kernel of its own that applies the output quantizer on its learned
+        grid -- no enabled input or parameter quantizer, and exactly one output quantizer, enabled,
+        per-tensor, integer, with its range set (one float32 element an end, on the GPU)."""
+        if any(q.enabled for q in self.input_quantizers) or any(q.enabled for q in self.param_quantizers.values()):
+            return False
+        if len(self.output_quantizers) != 1:
+            return False
+        q = self.output_quantizers[0]
+        if not (q.enabled and type(q) is LearnedGridTensorQuantizer and q.data_type == QuantizationDataType.int and
+                q.bitwidth < 32):
+            return False
+        return all(r is not None and r.numel() == 1 and r.is_cuda and r.dtype == torch.float32 for r in self._ranges(q))
+
+    def fused_output_grid(self):
+        """One forward whose arithmetic the caller fuses (output_fusable() holds): the gate on the
+        ranges as forward() applies it, then (encoding_min, encoding_max, (bitwidth, use_symmetric,
+        use_strict_symmetric, is_unsigned_symmetric)) of the output quantizer -- the two trainable
+        parameters themselves, for the caller's autograd function."""
+        self.apply_gating_logic()
+        q = self.output_quantizers[0]
+        emin, emax = self._ranges(q)
+        return emin, emax, (q.bitwidth, q.use_symmetric_encodings, q.use_strict_symmetric, q.is_unsigned_symmetric)
+
     def compute_encoding(self):
         """Range-learning quantizers are initialised from a static-grid calibration (QuantSim
         replaces the wrappers after compute_encodings); they have no statistics of their own."""

@@ -23,7 +23,8 @@ exponential: the kernel's is written out in float32 operations, the literal rout
     (StaticGridQuantWrapper.output_fusable), the tensors are float32 on the GPU, no operand needs a
     gradient, and S <= aimet_attn_softmax_max_s(). In ANALYSIS mode the raw scores and the kernel's
     unquantized probabilities go to the two quantizers' statistics through the wrappers themselves.
-  * literal: the children called one by one. Everything else -- range learning / QAT, 16-bit or CPU
+  * literal: the children called one by one. Everything else -- range learning without the opt-in
+    below, per-channel or disabled learned quantizers, 16-bit or CPU
     tensors, float data types, stochastic rounding, enabled input quantizers, an unwrapped module,
     longer rows -- and `module.fused = False`.
   * fused with a gradient (opt-in, `module.fused_backward = True` or set_fused_attention_backward(model)):
@@ -33,10 +34,22 @@ exponential: the kernel's is written out in float32 operations, the literal rout
     straight-through masks, the softmax backward and the mask fills (the literal route keeps the raw
     scores, the softmax output and the unquantized probabilities, and runs an STE kernel, torch's
     softmax backward, the mask-fill backwards and a second STE kernel). Static-grid wrappers only: the
-    gradient of a calibrated sim, STE QAT with the post_training_* schemes. Range-learning wrappers
-    still take the literal route. The gradients of the two routes differ by float32 rounding and, where
-    exp_r and torch's exponential put a probability on neighbouring levels, by one level of softmax's
-    quantizer. Measured against the literal route in DESIGN section 5.
+    gradient of a calibrated sim, STE QAT with the post_training_* schemes. The gradients of the two
+    routes differ by float32 rounding and, where exp_r and torch's exponential put a probability on
+    neighbouring levels, by one level of softmax's quantizer. Measured against the literal route in
+    DESIGN section 5.
+  * fused, range learning (the same opt-in; without it range-learning wrappers take the literal route
+    with or without a gradient): matmul_1 and softmax are LearnedGridQuantWrappers whose forward is
+    nothing but one enabled per-tensor integer output quantizer (LearnedGridQuantWrapper.output_fusable).
+    Each wrapper's gate runs first, then AttnSoftmaxLearned: ONE aimet_attn_softmax_lg launch that reads
+    the four trainable range ends on the device (nothing comes back to the host), computes delta and
+    offset as the learned-grid kernels do, rounds half to even and keeps the raw scores and eight floats
+    of encodings; going back, ONE aimet_attn_softmax_lg_backward row launch recomputes each row, writes
+    the score gradient and carries the six sums of the two quantizers' range gradients, which a
+    one-workgroup second launch folds in a fixed order into d/d encoding_min and d/d encoding_max of
+    both (no atomics: equal inputs give equal bits). The literal route runs a learned-grid forward, the
+    mask fills, torch's softmax and a second learned-grid forward, and their four backwards, over four
+    saved tensors of the score's size.
 
 Masks: bool (or, deprecated, uint8) attn_mask of [L, S] or [B H, L, S] and key_padding_mask of [B, S],
 True = not attended. nn.TransformerEncoderLayer / DecoderLayer hand their masks on as float tensors
@@ -72,7 +85,7 @@ from torch.autograd.function import once_differentiable
 
 from aimet_amd import _native
 from aimet_amd.elementwise_ops import Add, Divide, MatMul
-from aimet_amd.qc_quantize_op import StaticGridQuantWrapper
+from aimet_amd.qc_quantize_op import LearnedGridQuantWrapper, StaticGridQuantWrapper
 
 _NEG_INF = float("-inf")
 
@@ -200,6 +213,122 @@ class AttnSoftmax(torch.autograd.Function):
         batch, num_heads, score_enc, prob_enc = ctx.args
         return (attn_softmax_backward(scores, grad_probs.contiguous(), batch, num_heads, attn_mask, key_padding_mask,
                                       score_enc, prob_enc),) + (None,) * 6
+
+
+# ---- the fused launches on learned grids (range learning) ------------------------------------------
+def attn_lg_launch_count(reset: bool = False) -> Tuple[int, int]:
+    """(aimet_attn_softmax_lg launches, aimet_attn_softmax_lg_backward row launches) issued in this
+    process; the backward's fold launch is not counted."""
+    fwd, bwd = ctypes.c_int64(0), ctypes.c_int64(0)
+    _native.call("aimet_attn_lg_launch_count", ctypes.byref(fwd), ctypes.byref(bwd), int(reset))
+    return fwd.value, bwd.value
+
+
+def _lg_grid_c(fn, grid, device, with_range):
+    """(encoding_min, encoding_max, bitwidth, use_symmetric, use_strict_symmetric, is_unsigned_symmetric)
+    -> aimet_attn_lg_grid; None stays None. The range is handed over by address: the kernel reads it."""
+    if grid is None:
+        return None
+    emin, emax, bw, sym, strict, unsigned = grid
+    if bw >= 32:
+        raise RuntimeError("Invalid bitwidth: %d" % bw)
+    ptrs = (None, None)
+    if with_range:
+        for name, r in (("encoding_min", emin), ("encoding_max", emax)):
+            if not (isinstance(r, Tensor) and r.is_cuda and r.device == device and r.dtype == torch.float32 and
+                    r.numel() == 1):
+                raise ValueError(fn + ": %s must be one float32 element on %s" % (name, device))
+        ptrs = (emin.data_ptr(), emax.data_ptr())
+    return _native.AttnLgGridC(*ptrs, int(bw), int(bool(sym)), int(bool(strict)), int(bool(unsigned)))
+
+
+def _ref(struct):
+    return ctypes.byref(struct) if struct is not None else None
+
+
+def attn_softmax_lg(scores: Tensor, batch: int, num_heads: int, attn_mask: Optional[Tensor] = None,
+                    key_padding_mask: Optional[Tensor] = None, score_grid=None, prob_grid=None,
+                    out: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """One aimet_attn_softmax_lg launch: attn_softmax with both quantizers on learned grids
+    (calculate_forward_pass). A grid is (encoding_min, encoding_max, bitwidth, use_symmetric,
+    use_strict_symmetric, is_unsigned_symmetric) with the range as two one-element float32 GPU tensors,
+    which the kernel reads (nothing comes back to the host), or None for no quantizer. Out of place.
+    Returns (probs, saved): saved [2, 4] holds {delta, offset, min, max} of the score grid (row 0) and
+    of the prob grid (row 1) as the kernel computed and read them, for attn_softmax_lg_backward; a row
+    without a quantizer is not written. There is no other implementation behind this function."""
+    others = {"out": out}
+    args, _alive = _launch_args("attn_softmax_lg", scores, batch, num_heads, attn_mask, key_padding_mask, None, None,
+                                others)
+    sg = _lg_grid_c("attn_softmax_lg", score_grid, scores.device, True)
+    pg = _lg_grid_c("attn_softmax_lg", prob_grid, scores.device, True)
+    saved = torch.empty((2, 4), dtype=torch.float32, device=scores.device)
+    with torch.cuda.device(scores.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _native.call("aimet_attn_softmax_lg", scores.data_ptr(), others["out"].data_ptr(), *args[:-2], _ref(sg),
+                     saved[0].data_ptr(), _ref(pg), saved[1].data_ptr(), stream)
+    return others["out"], saved
+
+
+def attn_softmax_lg_backward(scores: Tensor, grad_probs: Tensor, batch: int, num_heads: int,
+                             attn_mask: Optional[Tensor] = None, key_padding_mask: Optional[Tensor] = None,
+                             score_grid=None, prob_grid=None, saved: Optional[Tensor] = None,
+                             out: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """aimet_attn_softmax_lg_backward (the row launch and its fold): from the raw `scores`,
+    `grad_probs` and what attn_softmax_lg saved, (grad_scores, range_grads): range_grads [2, 2] holds
+    (d/d encoding_min, d/d encoding_max) of the score grid (row 0) and of the prob grid (row 1); a row
+    without a quantizer is not written. Of a grid only the bitwidth and the flags are read here.
+    `out` may be `grad_probs`. There is no other implementation behind this function."""
+    if grad_probs is None:
+        raise ValueError("attn_softmax_lg_backward: grad_probs must match scores")
+    others = {"grad_probs": grad_probs, "out": out}
+    args, _alive = _launch_args("attn_softmax_lg_backward", scores, batch, num_heads, attn_mask, key_padding_mask,
+                                None, None, others)
+    if not (isinstance(saved, Tensor) and saved.shape == (2, 4) and saved.dtype == torch.float32 and
+            saved.device == scores.device and saved.is_contiguous()):
+        raise ValueError("attn_softmax_lg_backward: saved must be the [2, 4] float32 tensor attn_softmax_lg returned")
+    sg = _lg_grid_c("attn_softmax_lg_backward", score_grid, scores.device, False)
+    pg = _lg_grid_c("attn_softmax_lg_backward", prob_grid, scores.device, False)
+    grads = torch.empty((2, 2), dtype=torch.float32, device=scores.device)
+    with torch.cuda.device(scores.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _native.call("aimet_attn_softmax_lg_backward", scores.data_ptr(), grad_probs.data_ptr(),
+                     others["out"].data_ptr(), *args[:-2], _ref(sg), saved[0].data_ptr(), grads[0].data_ptr(),
+                     _ref(pg), saved[1].data_ptr(), grads[1].data_ptr(), stream)
+    return others["out"], grads
+
+
+class AttnSoftmaxLearned(torch.autograd.Function):
+    """attn_softmax_lg with gradients for `scores` and for the four range ends: apply(scores, batch,
+    num_heads, attn_mask, key_padding_mask, score_min, score_max, score_flags, prob_min, prob_max,
+    prob_flags), flags = (bitwidth, use_symmetric, use_strict_symmetric, is_unsigned_symmetric), a None
+    range = no quantizer. The forward saves the raw scores, the masks and the eight floats of the two
+    encodings as the kernel read them (the range parameters may change before the backward: the
+    wrapper's gate writes them in place on every call). Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, scores, batch, num_heads, attn_mask, key_padding_mask, score_min, score_max, score_flags,
+                prob_min, prob_max, prob_flags):
+        grids = tuple(None if lo is None else (lo.detach(), hi.detach()) + tuple(flags)
+                      for lo, hi, flags in ((score_min, score_max, score_flags), (prob_min, prob_max, prob_flags)))
+        probs, saved = attn_softmax_lg(scores, batch, num_heads, attn_mask, key_padding_mask, *grids)
+        ctx.args = (batch, num_heads) + tuple(None if g is None else (None, None) + g[2:] for g in grids)
+        ctx.shapes = tuple(None if r is None else r.shape for r in (score_min, score_max, prob_min, prob_max))
+        ctx.save_for_backward(scores, attn_mask, key_padding_mask, saved)
+        return probs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_probs):
+        need = ctx.needs_input_grad
+        if not any(need):
+            return (None,) * 11
+        scores, attn_mask, key_padding_mask, saved = ctx.saved_tensors
+        batch, num_heads, score_grid, prob_grid = ctx.args
+        dx, grads = attn_softmax_lg_backward(scores, grad_probs.contiguous(), batch, num_heads, attn_mask,
+                                             key_padding_mask, score_grid, prob_grid, saved)
+        flat = grads.view(-1)
+        rg = [flat[i:i + 1].view(ctx.shapes[i]) if need[pos] else None for i, pos in enumerate((5, 6, 8, 9))]
+        return (dx if need[0] else None, None, None, None, None, rg[0], rg[1], None, rg[2], rg[3], None)
 
 
 # ---- masks ---------------------------------------------------------------------------------------
@@ -349,12 +478,16 @@ class QuantizableMultiheadAttention(nn.MultiheadAttention):
     # -- the attention probabilities --------------------------------------------------------------
     def _fused_route(self, q: Tensor, k: Tensor, src_len: int) -> bool:
         m1, sm = self.matmul_1, self.softmax
-        if not (self.fused and isinstance(m1, StaticGridQuantWrapper) and isinstance(sm, StaticGridQuantWrapper)):
+        opt_in = getattr(self, "fused_backward", False)
+        if isinstance(m1, LearnedGridQuantWrapper) and isinstance(sm, LearnedGridQuantWrapper):
+            allowed = opt_in   # range learning: the fused route is the opt-in one, with or without a gradient
+        elif isinstance(m1, StaticGridQuantWrapper) and isinstance(sm, StaticGridQuantWrapper):
+            allowed = opt_in or not (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad))
+        else:
+            return False
+        if not (self.fused and allowed):
             return False
         if not (q.is_cuda and q.dtype == torch.float32 and k.dtype == torch.float32 and k.device == q.device):
-            return False
-        if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad) and \
-                not getattr(self, "fused_backward", False):
             return False
         if not (m1.output_fusable() and sm.output_fusable()):
             return False
@@ -364,6 +497,13 @@ class QuantizableMultiheadAttention(nn.MultiheadAttention):
         scores = torch.bmm(q, k.transpose(1, 2))
         if attn_mask is not None and attn_mask.shape[0] == 1:
             attn_mask = attn_mask[0]   # one [L, S] table for every batch entry and head
+        if isinstance(self.matmul_1, LearnedGridQuantWrapper):
+            # range learning: each wrapper's gate first, as its forward() runs it; then one launch that
+            # reads the four range parameters on the device
+            score_min, score_max, score_flags = self.matmul_1.fused_output_grid()
+            prob_min, prob_max, prob_flags = self.softmax.fused_output_grid()
+            return AttnSoftmaxLearned.apply(scores, bsz, self.num_heads, attn_mask, key_padding_mask, score_min,
+                                            score_max, score_flags, prob_min, prob_max, prob_flags)
         if getattr(self, "fused_backward", False):
             # the statistics (ANALYSIS) see the tensors outside the graph; never in place
             score_enc = self.matmul_1.fused_output_encoding()

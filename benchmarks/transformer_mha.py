@@ -18,6 +18,12 @@ output difference between the routes, and aimet_attn_softmax alone on the block'
 time per launch between two events over back-to-back launches, and the 8 bytes an element it has to
 move (one float32 read, one written) over that time as a fraction of the MI355X's 8 TB/s; the same for
 aimet_attn_softmax_backward against its 12 bytes an element (scores and gradient read, gradient written).
+  * RL-TRAIN (--rows range_learning): the same block under training_range_learning_with_tf_init, one
+    forward plus backward with a gradient for the input, every weight and every range, `fused_backward`
+    on (AttnSoftmaxLearned: aimet_attn_softmax_lg and aimet_attn_softmax_lg_backward, one row launch
+    each way) and off (the literal route), with the peak memory and the largest differences of the input
+    gradient and of the four range gradients of matmul_1 and softmax between the routes; then the two
+    kernels alone, as above (8 and 12 bytes an element; the backward's time includes its fold launch).
 One JSON line at the end.
 """
 import argparse
@@ -35,6 +41,7 @@ if REPO not in sys.path:
 
 from aimet_amd import transformers as T  # noqa: E402
 from aimet_amd.elementwise_ops import TRANSFORMER_QUANTIZABLE_TYPES  # noqa: E402
+from aimet_amd.quantizers import QuantScheme  # noqa: E402
 from aimet_amd.quantsim import QuantizationSimModel  # noqa: E402
 
 SHAPES = {"vit": dict(E=1024, H=16, L=197, B=64), "long": dict(E=1024, H=16, L=2048, B=4)}
@@ -72,8 +79,90 @@ def kernel_alone(B, H, L, S, encodings, launches, backward=False):
     return e0.elapsed_time(e1) / launches
 
 
+def learned_kernels_alone(B, H, L, S, launches):
+    """Milliseconds per aimet_attn_softmax_lg launch and per aimet_attn_softmax_lg_backward call (the row launch
+    and its fold) on [B H, L, S], both quantizers at 8 bits asymmetric, out of place, back to back."""
+    scores = torch.randn(B * H, L, S, device="cuda") * 3.0
+    grad, out = torch.randn_like(scores), torch.empty_like(scores)
+    ends = [torch.tensor([v], device="cuda") for v in (-8.0, 127.0 / 16.0, 0.0, 255.0 / 256.0)]
+    grids = [(ends[0], ends[1], 8, False, False, False), (ends[2], ends[3], 8, False, False, False)]
+    saved = T.attn_softmax_lg(scores, B, H, None, None, *grids, out=out)[1]
+    ms = []
+    for run in (lambda: T.attn_softmax_lg(scores, B, H, None, None, *grids, out=out),
+                lambda: T.attn_softmax_lg_backward(scores, grad, B, H, None, None, *grids, saved, out=out)):
+        for _ in range(5):
+            run()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(launches):
+            run()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / launches)
+    return ms
+
+
 def spread(v):
     return {"ms": statistics.median(v), "min": min(v), "max": max(v)}
+
+
+def range_learning_train(name, s, runs, lines, launches):
+    """The RL-TRAIN row of shape `name` and the two range-learning kernels alone -> its results."""
+    E, H, L, B = s["E"], s["H"], s["L"], s["B"]
+    attn = T.QuantizableMultiheadAttention(E, H).cuda().eval()
+    x = torch.randn(L, B, E, device="cuda")
+    sim = QuantizationSimModel(attn, dummy_input=(x, x, x),
+                               quant_scheme=QuantScheme.training_range_learning_with_tf_init,
+                               quantizable_types=TRANSFORMER_QUANTIZABLE_TYPES)
+    sim.compute_encodings(lambda model, _: model(x, x, x, need_weights=False))
+    m = sim.model
+    grad_out = torch.randn(L, B, E, device="cuda")
+    ranges = [getattr(getattr(m, w), "output0_encoding_" + e) for w in ("matmul_1", "softmax") for e in ("min", "max")]
+
+    def train(fused_backward):
+        m.fused_backward = fused_backward
+        m.zero_grad(set_to_none=True)
+        xg = x.clone().requires_grad_(True)
+        m(xg, xg, xg, need_weights=False)[0].backward(grad_out)
+        return xg.grad, [float(p.grad) for p in ranges]
+    n0 = T.attn_lg_launch_count()
+    g_f, r_f = train(True)
+    r = {"launches_per_train_step": [b - a for a, b in zip(n0, T.attn_lg_launch_count())]}
+    g_l, r_l = train(False)
+    r["grad_max_abs_diff"], r["grad_max_abs"] = float((g_f - g_l).abs().max()), float(g_l.abs().max())
+    r["range_grads_fused"], r["range_grads_literal"] = r_f, r_l
+    del g_f, g_l
+    times, peak = {True: [], False: []}, {}
+    for _ in range(runs):
+        for fb in (True, False):
+            torch.cuda.reset_peak_memory_stats()
+            times[fb].append(timed(lambda: train(fb)))
+            peak[fb] = torch.cuda.max_memory_allocated()
+    r.update({"fused": spread(times[True]), "literal": spread(times[False]),
+              "literal_over_fused": statistics.median(times[False]) / statistics.median(times[True]),
+              "fused_peak_bytes": peak[True], "literal_peak_bytes": peak[False]})
+    f, l = r["fused"], r["literal"]
+    lines.append("%-4s E %d H %d L=S %d B %d  %-8s fused %8.2f [%8.2f .. %8.2f]   literal %8.2f [%8.2f .. %8.2f]   "
+                 "literal / fused %.2f   peak memory fused %.0f MB, literal %.0f MB"
+                 % (name, E, H, L, B, "RL-TRAIN", f["ms"], f["min"], f["max"], l["ms"], l["min"], l["max"],
+                    r["literal_over_fused"], peak[True] / 1e6, peak[False] / 1e6))
+    lines.append("%-4s range learning: largest input-gradient difference between the routes %.3g of %.3g; range "
+                 "gradients (matmul_1 min, max, softmax min, max) fused %s, literal %s; launches per fused training "
+                 "step: %d forward, %d backward" % (name, r["grad_max_abs_diff"], r["grad_max_abs"],
+                                                    " ".join("%.6g" % v for v in r_f),
+                                                    " ".join("%.6g" % v for v in r_l), *r["launches_per_train_step"]))
+    m.fused_backward = False
+    del sim, m, attn, grad_out
+    torch.cuda.empty_cache()
+    alone = learned_kernels_alone(B, H, L, L, launches)
+    for key, ms, nbytes in zip(("lg_kernel", "lg_backward_kernel"), alone, (8, 12)):
+        moved = float(nbytes) * B * H * L * L
+        r[key] = {"ms": ms, "bytes": moved, "fraction_of_8TBs": moved / (ms * 1e-3) / HBM_BYTES_PER_S}
+        lines.append("%-4s aimet_attn_softmax_%s alone on [%d, %d, %d], both grids: %.3f ms, %.0f MB read + written, "
+                     "%.2f of 8 TB/s" % (name, "lg" if nbytes == 8 else "lg_backward (rows and fold)", B * H, L, L, ms,
+                                         moved / 1e6, r[key]["fraction_of_8TBs"]))
+    return r
 
 
 def main():
@@ -81,6 +170,7 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--shapes", default="vit,long")
     ap.add_argument("--kernel-launches", type=int, default=50)
+    ap.add_argument("--rows", default="static,range_learning")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs an MI355X"
@@ -91,6 +181,11 @@ def main():
     for name in a.shapes.split(","):
         s = SHAPES[name]
         E, H, L, B = s["E"], s["H"], s["L"], s["B"]
+        if "static" not in a.rows.split(","):
+            result[name] = dict(s, elements=B * H * L * L, range_learning_train=range_learning_train(
+                name, s, a.runs, lines, a.kernel_launches))
+            torch.cuda.empty_cache()
+            continue
         attn = T.QuantizableMultiheadAttention(E, H).cuda().eval()
         x = torch.randn(L, B, E, device="cuda")
         sim = QuantizationSimModel(attn, dummy_input=(x, x, x), quant_scheme="tf",
@@ -182,6 +277,9 @@ def main():
                                                          bytes_moved / 1e6, r[key]["bytes_per_s"] / 1e12,
                                                          r[key]["fraction_of_8TBs"]))
         torch.cuda.empty_cache()
+        if "range_learning" in a.rows.split(","):
+            r["range_learning_train"] = range_learning_train(name, s, a.runs, lines, a.kernel_launches)
+            torch.cuda.empty_cache()
     text = "\n".join(lines) + "\n" + json.dumps(result, sort_keys=True) + "\n"
     sys.stdout.write(text)
     if a.out:

@@ -1107,6 +1107,51 @@ int aimet_attn_softmax_backward(const float* scores, const float* grad_probs, fl
  * counts forward launches only); reset != 0 zeroes it. */
 int aimet_attn_backward_launch_count(int64_t* count, int reset);
 
+/* The same launch for range learning (LearnedGridQuantWrapper): both quantizers on learned grids, the
+ * arithmetic of aimet_lg_forward_range / aimet_lg_backward (calculate_forward_pass, asymmetric_gradients,
+ * symmetric_gradients; round half to even). A grid names its trainable range by two device pointers (one
+ * float each), read by the kernel and never by the host, so the call can be captured; bitwidth and the
+ * three flags are aimet_lg_forward_range's. A NULL grid skips that quantizer.
+ *   forward:  x_j = lg_qdq(scores_j; score grid), masks, m, e_j, s, p_j = e_j / s as aimet_attn_softmax
+ *             (same summation orders, same S bound), probs_j = lg_qdq(p_j; prob grid). Out of place. Each
+ *             quantizer's {delta, offset, min, max} as the kernel read and computed them go to its
+ *             4-float device buffer `saved` for the backward.
+ *   backward: from the raw scores, g at the quantized probabilities and the two saved encodings (the
+ *             range pointers of the grids are not read). p_j recomputed bit for bit; then, with
+ *             q = p_j / delta_p and the in-grid mask m_p of it, G_j = m_p g_j; d = sum_j G_j p_j in the
+ *             order of s; t_j = (G_j - d) p_j; grad_scores_j = m_s t_j with m_s the in-grid mask of
+ *             scores_j / delta_s. A masked position gets exactly 0 and adds nothing to any sum. The sums
+ *             {A, B, D} of aimet_lg_backward are taken for the probability quantizer with gradient g_j and
+ *             for the score quantizer with gradient t_j, and range_grad[0] / [1] (device, two floats a
+ *             quantizer) receive the gradients of encoding_min / encoding_max by aimet_lg_range_grads'
+ *             expressions on the saved range. Two launches: the rows, one partial of six sums a
+ *             workgroup; then one workgroup that folds the partials in a fixed order (with both grids NULL
+ *             there are no sums and no second launch). No atomics: equal inputs give equal bits.
+ *             grad_scores may be grad_probs. */
+typedef struct aimet_attn_lg_grid
+{
+    const float* encoding_min;
+    const float* encoding_max;
+    int bitwidth;
+    int use_symmetric;
+    int use_strict_symmetric;
+    int is_unsigned_symmetric;
+} aimet_attn_lg_grid;
+int aimet_attn_softmax_lg(const float* scores, float* probs, int64_t B, int64_t H, int64_t L, int64_t S,
+                          const uint8_t* attn_mask, int attn_mask_per_bh, const uint8_t* key_padding_mask,
+                          const aimet_attn_lg_grid* score_grid, float* score_saved, const aimet_attn_lg_grid* prob_grid,
+                          float* prob_saved, void* stream);
+int aimet_attn_softmax_lg_backward(const float* scores, const float* grad_probs, float* grad_scores, int64_t B,
+                                   int64_t H, int64_t L, int64_t S, const uint8_t* attn_mask, int attn_mask_per_bh,
+                                   const uint8_t* key_padding_mask, const aimet_attn_lg_grid* score_grid,
+                                   const float* score_saved, float* score_range_grad,
+                                   const aimet_attn_lg_grid* prob_grid, const float* prob_saved, float* prob_range_grad,
+                                   void* stream);
+
+/* Launches of aimet_attn_softmax_lg (*forward) and row launches of aimet_attn_softmax_lg_backward
+ * (*backward; its fold is not counted) in this process; either pointer may be NULL; reset != 0 zeroes both. */
+int aimet_attn_lg_launch_count(int64_t* forward, int64_t* backward, int reset);
+
 /* ---- PEFT LoRA adapters in QuantSim (aimet_torch/peft.py LoraLayer) -------------------------------
  * The element-wise tail of an adapted layer, one launch each, equal bit for bit to the wrapped children
  * called one by one (csrc/lora.hip states every rounding). All tensors of a call hold n elements of one
