@@ -296,6 +296,9 @@ _PROTOTYPES = {
     "aimet_attn_softmax_lg_backward": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _vp, _lg_grid_p, _vp, _vp,
                                        _lg_grid_p, _vp, _vp, _vp],
     "aimet_attn_lg_launch_count": [_i64p, _i64p, _int],
+    "aimet_attn_core": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _int,
+                        _vp, _enc_p, _enc_p, _enc_p, _vp],
+    "aimet_attn_core_launch_count": [_i64p, _int],
     "aimet_lora_merge": [_vp, _vp, _vp, _i64, _int, _enc_p, _enc_p, _enc_p, _vp],
     "aimet_lora_merge_backward": [_vp, _vp, _vp, _vp, _vp, _i64, _int, _enc_p, _enc_p, _enc_p, _vp],
     "aimet_lora_scale": [_vp, _vp, _i64, _int, ctypes.c_float, _enc_p, _enc_p, _vp],

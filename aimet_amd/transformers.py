@@ -38,6 +38,18 @@ exponential: the kernel's is written out in float32 operations, the literal rout
     routes differ by float32 rounding and, where exp_r and torch's exponential put a probability on
     neighbouring levels, by one level of softmax's quantizer. Measured against the literal route in
     DESIGN section 5.
+  * fused core (opt-in, `module.fused_core = True` or set_fused_attention_core(model)): ONE aimet_attn_core
+    launch (csrc/attn_core.hip) computes q k^T, matmul_1's output quantizer, the masks, the softmax,
+    softmax's output quantizer, the product with v and matmul_2's output quantizer on the fp32 matrix
+    cores, and the [B H, L, S] scores and probabilities never reach memory: rows of any length, where
+    the fused route stops at aimet_attn_softmax_max_s() and the literal route needs several tensors of
+    that size. Taken when need_weights is false, dropout is inactive, no gradient is wanted, matmul_1,
+    softmax and matmul_2 are static-grid wrappers with output_fusable() in ACTIVE or PASSTHROUGH mode
+    (ANALYSIS needs the score statistics), the tensors are float32 on one GPU and head_dim is 32, 64 or
+    128; otherwise the route is chosen as without it. The score product is computed twice, and below
+    aimet_attn_softmax_max_s() this route is not faster than the fused one; nothing
+    switches automatically. Its probabilities are those of the fused route but for the order of the
+    row sum.
   * fused, range learning (the same opt-in; without it range-learning wrappers take the literal route
     with or without a gradient): matmul_1 and softmax are LearnedGridQuantWrappers whose forward is
     nothing but one enabled per-tensor integer output quantizer (LearnedGridQuantWrapper.output_fusable).
@@ -85,7 +97,7 @@ from torch.autograd.function import once_differentiable
 
 from aimet_amd import _native
 from aimet_amd.elementwise_ops import Add, Divide, MatMul
-from aimet_amd.qc_quantize_op import LearnedGridQuantWrapper, StaticGridQuantWrapper
+from aimet_amd.qc_quantize_op import LearnedGridQuantWrapper, QcQuantizeOpMode, StaticGridQuantWrapper
 
 _NEG_INF = float("-inf")
 
@@ -213,6 +225,83 @@ class AttnSoftmax(torch.autograd.Function):
         batch, num_heads, score_enc, prob_enc = ctx.args
         return (attn_softmax_backward(scores, grad_probs.contiguous(), batch, num_heads, attn_mask, key_padding_mask,
                                       score_enc, prob_enc),) + (None,) * 6
+
+
+# ---- the attention core: no score tensor ------------------------------------------------------------
+ATTN_CORE_HEAD_DIMS = (32, 64, 128)   # the instantiations of csrc/attn_core.hip
+
+
+def attn_core_launch_count(reset: bool = False) -> int:
+    """aimet_attn_core launches issued in this process."""
+    n = ctypes.c_int64(0)
+    _native.call("aimet_attn_core_launch_count", ctypes.byref(n), int(reset))
+    return n.value
+
+
+def _extent(t: Tensor) -> Tuple[int, int]:
+    """[first byte, one past the last byte) that the view `t` can touch."""
+    last = sum((n - 1) * s for n, s in zip(t.shape, t.stride()))
+    return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
+
+
+def attn_core(q: Tensor, k: Tensor, v: Tensor, batch: int, num_heads: int, attn_mask: Optional[Tensor] = None,
+              key_padding_mask: Optional[Tensor] = None, score_enc=None, prob_enc=None, out_enc=None,
+              out: Optional[Tensor] = None) -> Tensor:
+    """One aimet_attn_core launch (csrc/attn_core.hip): for q [batch * num_heads, L, D] and k, v
+    [batch * num_heads, S, D] (float32, GPU; transposed views with D contiguous are read in place),
+    out = QDQ(out_enc)( QDQ(prob_enc)( softmax( mask( QDQ(score_enc)(q k^T) ) ) ) v ) as a contiguous
+    [batch * num_heads, L, D] tensor, without the [.., L, S] scores or probabilities ever reaching memory.
+    Masks and encodings as attn_softmax takes them; D must be one of ATTN_CORE_HEAD_DIMS; S is not
+    bounded. `out` must not overlap an input. There is no other implementation behind this function.
+
+    The score product is computed twice (3 * 2 * B H L S D matrix FLOPs) and the exponential of every
+    element twice; DESIGN section 5 has it measured against the route that keeps the scores in memory:
+    where that route can run (S <= attn_softmax_max_s()) this one is not faster (0.91 of its speed at
+    L = S = 2048, not told apart at a ViT-L block), and it is the only fused one beyond. Nothing switches
+    between the routes automatically."""
+    fn = "attn_core"
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not (isinstance(t, Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3):
+            raise ValueError(fn + ": %s must be a float32 [B H, rows, D] tensor on the GPU" % name)
+    BH, L, D = q.shape
+    S = k.shape[1]
+    if BH != batch * num_heads:
+        raise ValueError(fn + ": q has %d matrices, batch * num_heads is %d" % (BH, batch * num_heads))
+    if tuple(k.shape) != (BH, S, D) or tuple(v.shape) != (BH, S, D) or k.device != q.device or v.device != q.device:
+        raise ValueError(fn + ": k and v must be [%d, S, %d] tensors on %s" % (BH, D, q.device))
+    if D not in ATTN_CORE_HEAD_DIMS:
+        raise ValueError(fn + ": head_dim %d is not supported (%s)" % (D, ", ".join(map(str, ATTN_CORE_HEAD_DIMS))))
+    if L == 0 or S == 0 or BH == 0:
+        raise ValueError(fn + ": empty q, k or v")
+    if out is None:
+        out = torch.empty((BH, L, D), dtype=torch.float32, device=q.device)
+    elif not (isinstance(out, Tensor) and out.is_cuda and out.dtype == torch.float32 and out.device == q.device and
+              tuple(out.shape) == (BH, L, D) and out.is_contiguous()):
+        raise ValueError(fn + ": out must be a contiguous float32 [%d, %d, %d] tensor on %s" % (BH, L, D, q.device))
+    lo, hi = _extent(out)
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        t_lo, t_hi = _extent(t)
+        if t_lo < hi and lo < t_hi:
+            raise ValueError(fn + ": out must not overlap %s" % name)
+
+    def operand(t):   # what the kernel's 16-byte loads need; anything else is copied once
+        ok = t.stride(2) == 1 and t.stride(0) % 4 == 0 and t.stride(1) % 4 == 0 and t.stride(1) >= D and \
+            t.data_ptr() % 16 == 0
+        return t if ok else t.clone(memory_format=torch.contiguous_format)
+
+    q, k, v = operand(q), operand(k), operand(v)
+    per_bh = attn_mask is not None and attn_mask.dim() == 3
+    am = _mask_bytes(attn_mask, (BH, L, S) if per_bh else (L, S), q.device, "attn_mask", fn)
+    kpm = _mask_bytes(key_padding_mask, (batch, S), q.device, "key_padding_mask", fn)
+    encs = [_encoding_c(e) for e in (score_enc, prob_enc, out_enc)]
+    with torch.cuda.device(q.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _native.call("aimet_attn_core", q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), batch, num_heads, L,
+                     S, D, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
+                     am.data_ptr() if am is not None else None, int(per_bh),
+                     kpm.data_ptr() if kpm is not None else None,
+                     *[ctypes.byref(e) if e is not None else None for e in encs], stream)
+    return out
 
 
 # ---- the fused launches on learned grids (range learning) ------------------------------------------
@@ -407,6 +496,9 @@ class QuantizableMultiheadAttention(nn.MultiheadAttention):
         # AttnSoftmax: out of place, one more score-size tensor than the in-place launch; turn it off
         # for evaluation where that matters.
         self.fused_backward = False
+        # The whole attention core in one launch that keeps scores and probabilities on chip (attn_core;
+        # module docstring). Opt-in: evaluation only, and not faster than the fused route where that one runs.
+        self.fused_core = False
 
     def _get_name(self):
         return "QuantizableMultiheadAttention"
@@ -460,12 +552,16 @@ class QuantizableMultiheadAttention(nn.MultiheadAttention):
             attn_mask, key_padding_mask = _pad_column(attn_mask), _pad_column(key_padding_mask)
         src_len = k.shape[1]
 
-        if self._fused_route(q, k, src_len):
-            probs = self._fused_probs(q, k, bsz, attn_mask, key_padding_mask)
+        if self._core_route(q, k, v, need_weights):
+            probs = None
+            out = self._core_out(q, k, v, bsz, attn_mask, key_padding_mask)
         else:
-            probs = self._literal_probs(q, k, bsz, attn_mask, key_padding_mask)
-        probs = F.dropout(probs, p=self.dropout, training=self.training)   # after softmax's quantizer
-        out = self.matmul_2(probs, v)                                      # [B H, L, head_dim]
+            if self._fused_route(q, k, src_len):
+                probs = self._fused_probs(q, k, bsz, attn_mask, key_padding_mask)
+            else:
+                probs = self._literal_probs(q, k, bsz, attn_mask, key_padding_mask)
+            probs = F.dropout(probs, p=self.dropout, training=self.training)   # after softmax's quantizer
+            out = self.matmul_2(probs, v)                                      # [B H, L, head_dim]
         out = out.transpose(0, 1).contiguous().view(tgt_len, bsz, self.embed_dim)
         out = self.out_proj(out)
         if self.batch_first:
@@ -474,6 +570,31 @@ class QuantizableMultiheadAttention(nn.MultiheadAttention):
             return out, None
         probs = probs.view(bsz, heads, tgt_len, src_len)
         return out, (probs.mean(dim=1) if average_attn_weights else probs)
+
+    # -- the attention core in one launch ------------------------------------------------------------
+    def _core_route(self, q: Tensor, k: Tensor, v: Tensor, need_weights: bool) -> bool:
+        if not getattr(self, "fused_core", False) or need_weights:
+            return False
+        if self.dropout > 0.0 and self.training:
+            return False
+        if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+            return False
+        wrappers = (self.matmul_1, self.softmax, self.matmul_2)
+        if not all(isinstance(w, StaticGridQuantWrapper) and w.output_fusable() for w in wrappers):
+            return False
+        if any(w._mode not in (QcQuantizeOpMode.ACTIVE, QcQuantizeOpMode.PASSTHROUGH) for w in wrappers):
+            return False   # ANALYSIS: the statistics need the scores and the probabilities
+        if not all(t.is_cuda and t.dtype == torch.float32 and t.device == q.device for t in (q, k, v)):
+            return False
+        return self.softmax.get_original_module().dim in (-1, 2) and q.shape[2] in ATTN_CORE_HEAD_DIMS
+
+    def _core_out(self, q, k, v, bsz, attn_mask, key_padding_mask):
+        if attn_mask is not None and attn_mask.shape[0] == 1:
+            attn_mask = attn_mask[0]   # one [L, S] table for every batch entry and head
+        score_enc = self.matmul_1.fused_output_encoding()
+        prob_enc = self.softmax.fused_output_encoding()
+        out_enc = self.matmul_2.fused_output_encoding()
+        return attn_core(q, k, v, bsz, self.num_heads, attn_mask, key_padding_mask, score_enc, prob_enc, out_enc)
 
     # -- the attention probabilities --------------------------------------------------------------
     def _fused_route(self, q: Tensor, k: Tensor, src_len: int) -> bool:
@@ -641,6 +762,15 @@ def set_fused_attention_backward(model: nn.Module, enabled: bool = True) -> int:
     blocks = [m for m in model.modules() if isinstance(m, QuantizableMultiheadAttention)]
     for m in blocks:
         m.fused_backward = bool(enabled)
+    return len(blocks)
+
+
+def set_fused_attention_core(model: nn.Module, enabled: bool = True) -> int:
+    """Sets `fused_core` on every QuantizableMultiheadAttention of `model` (a QuantizationSimModel's
+    .model included); returns how many there are."""
+    blocks = [m for m in model.modules() if isinstance(m, QuantizableMultiheadAttention)]
+    for m in blocks:
+        m.fused_core = bool(enabled)
     return len(blocks)
 
 

@@ -1152,6 +1152,27 @@ int aimet_attn_softmax_lg_backward(const float* scores, const float* grad_probs,
  * (*backward; its fold is not counted) in this process; either pointer may be NULL; reset != 0 zeroes both. */
 int aimet_attn_lg_launch_count(int64_t* forward, int64_t* backward, int reset);
 
+/* The attention core for static-grid evaluation in one launch that writes neither scores nor
+ * probabilities: per query row (bh, l), b = bh / H, in float32,
+ *   out[bh][l][:] = QDQ_out( QDQ_prob( softmax_j( mask( QDQ_score( q[bh][l][:] . k[bh][j][:] ) ) ) ) v[bh][j][:] )
+ * with the QDQ, the masks (one byte an element, either may be NULL), exp_r, the IEEE divide, the exact
+ * 0 of a masked position and the NaN of a fully masked row of aimet_attn_softmax; a NULL encoding skips
+ * its QDQ. Both products run on the fp32 matrix cores; the key and value tiles stream through LDS and the
+ * kernel makes two passes over them (maximum and sum, then probabilities times v). The order of the row
+ * sum depends on S alone (csrc/attn_core.hip): equal inputs give equal bits. No atomics, no scratch.
+ *   q [B H, L, D], k and v [B H, S, D]: float32 on the device, D contiguous, 16-byte aligned, the strides
+ *   (in floats) between matrices and between rows given and multiples of 4; out [B H, L, D] contiguous.
+ *   D must be 32, 64 or 128; L and S are arbitrary (S is not bounded by AIMET_ATTN_SOFTMAX_MAX_S).
+ * Anything else returns AIMET_ERR_INVALID_ARGUMENT and nothing is written. */
+int aimet_attn_core(const float* q, const float* k, const float* v, float* out, int64_t B, int64_t H, int64_t L,
+                    int64_t S, int64_t D, int64_t q_bh_stride, int64_t q_row_stride, int64_t k_bh_stride,
+                    int64_t k_row_stride, int64_t v_bh_stride, int64_t v_row_stride, const uint8_t* attn_mask,
+                    int attn_mask_per_bh, const uint8_t* key_padding_mask, const aimet_tf_encoding* score_enc,
+                    const aimet_tf_encoding* prob_enc, const aimet_tf_encoding* out_enc, void* stream);
+
+/* Kernel launches aimet_attn_core has issued in this process; reset != 0 zeroes it. */
+int aimet_attn_core_launch_count(int64_t* count, int reset);
+
 /* ---- PEFT LoRA adapters in QuantSim (aimet_torch/peft.py LoraLayer) -------------------------------
  * The element-wise tail of an adapted layer, one launch each, equal bit for bit to the wrapped children
  * called one by one (csrc/lora.hip states every rounding). All tensors of a call hold n elements of one
