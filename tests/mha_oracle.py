@@ -5,6 +5,10 @@ quantizable multi-head attention built on it (aimet_amd/transformers.py), for th
    oracle, the masks, exp_r of rnn_math.hpp (tests/rnn_oracle.py), the documented summation order
    (strided lane sums, the xor butterfly, the pair of pairs above 1024 columns) and the IEEE divide.
    Equal inputs give equal bits.
+ * core_row_sums() / core_softmax_rows() / attn_core(): the same for the attention core
+   (aimet_amd/csrc/attn_core.hip), whose row sum runs over key tiles against a running maximum: four
+   lane groups a row, 16 values a lane a tile in increasing j, the rescaled carry across tiles, two
+   butterfly steps. Its two products run in float64 and round once, like the GEMMs below.
  * mha_forward(): the whole module in ACTIVE mode with every quantizer of the default layout (the
    output quantizer of each child, the weight quantizer of each linear). Its GEMMs run in float64
    and round once: the fixtures (tests/golden/make_golden_mha.py) are built so that every GEMM sum
@@ -72,9 +76,89 @@ def attn_softmax(scores, B, H, L, S, attn_mask=None, per_bh=False, key_padding_m
     return p
 
 
-# ---- the module --------------------------------------------------------------------------------
 def _gemm(a, b):
     return (a.astype(np.float64) @ b.astype(np.float64)).astype(F)
+
+
+# ---- the attention core (aimet_amd/csrc/attn_core.hip) -------------------------------------------------
+CORE_TILE = 64   # keys a tile: four subtiles of 16, lane group g of a row holding keys 4 g .. 4 g + 3 of each
+
+
+def core_row_sums(x, trace=None):
+    """x: [R, S] float32 rows, quantized and masked (-inf) -> (m [R], s [R]): the row maximum and the row
+    sum in the order the kernel's header documents. It takes x, not e: every e_j is formed against the
+    running maximum of its tile, so the sum is no function of the final exponentials.
+    trace(t, m_before, m_after, l_carried [R, 4]) sees every tile's carry before the tile's own sum is added."""
+    x = np.asarray(x, F)
+    R, S = x.shape
+    n = -(-S // CORE_TILE)
+    pad = np.full((R, n * CORE_TILE), -np.inf, F)   # a key past S is -inf as a score and adds +0
+    pad[:, :S] = x
+    pad = pad.reshape(R, n, 4, 4, 4)                # [row, tile, subtile st, lane group g, u]
+    m, l = np.full(R, -np.inf, F), np.zeros((R, 4), F)
+    with np.errstate(all="ignore"):
+        for t in range(n):
+            xt = pad[:, t]
+            mn = np.maximum(m, xt.max(axis=(1, 2, 3)))
+            e = np.where(xt == F(-np.inf), F(0), exp_r(xt - mn[:, None, None, None])).astype(F)
+            ts = e[:, 0, :, 0]                      # lane g: its 16 values in increasing j, from the first
+            for st in range(4):
+                for u in range(4):
+                    if st or u:
+                        ts = ts + e[:, st, :, u]
+            scaled = np.where((m == F(-np.inf))[:, None], F(0), l * exp_r(m - mn)[:, None]).astype(F)
+            l = np.where((mn == m)[:, None], l, scaled)
+            if trace is not None:
+                trace(t, m, mn, l)
+            l = l + ts
+            m = mn
+    return m, (l[:, 0] + l[:, 2]) + (l[:, 1] + l[:, 3])
+
+
+def core_softmax_rows(x):
+    """softmax_rows() in the core's order: unquantized probabilities of quantized and masked rows x [R, S];
+    NaN in a row with every position masked (0 / 0)."""
+    x = np.asarray(x, F)
+    m, s = core_row_sums(x)
+    with np.errstate(all="ignore"):
+        e = np.where(x == F(-np.inf), F(0), exp_r(x - m[:, None])).astype(F)
+        return e / s[:, None]
+
+
+def core_scores(q, k, B, H, attn_mask=None, per_bh=False, key_padding_mask=None, score_enc=None):
+    """q [B H, L, D], k [B H, S, D] -> the quantized and masked scores [B H, L, S]. The product runs in
+    float64 and rounds once: the kernel's bits only where every partial sum is exact in float32."""
+    q, k = np.asarray(q, F), np.asarray(k, F)
+    BH, L, S = q.shape[0], q.shape[1], k.shape[1]
+    assert BH == B * H
+    x = np.stack([_gemm(q[i], k[i].T) for i in range(BH)])
+    if score_enc is not None:
+        x = qdq(x, score_enc)
+    if attn_mask is not None:
+        x = np.where(np.asarray(attn_mask, bool).reshape((BH, L, S) if per_bh else (1, L, S)), F(-np.inf), x)
+    if key_padding_mask is not None:
+        kpm = np.repeat(np.asarray(key_padding_mask, bool).reshape(B, 1, 1, S), H, axis=1).reshape(BH, 1, S)
+        x = np.where(kpm, F(-np.inf), x)
+    return x
+
+
+def attn_core(q, k, v, B, H, attn_mask=None, per_bh=False, key_padding_mask=None, score_enc=None, prob_enc=None,
+              out_enc=None):
+    """What one aimet_attn_core launch computes: out [B H, L, D]. Masks and encodings as attn_softmax takes
+    them. Both products run in float64 and round once (see core_scores); between them the kernel's header
+    operation for operation."""
+    x = core_scores(q, k, B, H, attn_mask, per_bh, key_padding_mask, score_enc)
+    BH, L, S = x.shape
+    p = core_softmax_rows(x.reshape(BH * L, S)).reshape(BH, L, S)
+    if prob_enc is not None:
+        p = qdq(p, prob_enc)
+    v = np.asarray(v, F)
+    with np.errstate(all="ignore"):
+        out = np.stack([_gemm(p[i], v[i]) for i in range(BH)])
+    return qdq(out, out_enc) if out_enc is not None else out
+
+
+# ---- the module --------------------------------------------------------------------------------
 
 
 def _q(x, enc):
